@@ -102,6 +102,77 @@ def fullcheck_window_reads(capi, arrs, ends, pos64, a, b):
     return fullcheck.window_reads(capi, arrs, ends, pos64, int((ends - pos64).max()) if len(pos64) else 0, a, b)
 
 
+DUMP_SEED = 20240917           # the sample of --dump-outputs: the same windows / sites on every run with the same arguments
+DUMP_WINDOWS, DUMP_WINDOW_LEN, DUMP_SITES = 64, 256, 2048
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(np, capi, eng, out_dir, suffix, n_lib, region_len, sites=None, site_vbeg0=None):
+    """--dump-outputs: what the timed path computed in its last step, as a caller of that path receives it, one float32 / float64
+    .npy file per array (integers as float64: exact).  weak / strong: the engine's result over a fixed, seeded sample of windows of
+    the timed region (brc_fetch_window: no second computation) — per position and library ncol, depth, istat, fstat, unavail and
+    the reference base, per window its events and indel buckets (key fields, statistics, allele bytes); sites: the lines of a fixed,
+    seeded sample of the sites, cut out as the planner does.  region_counts: events and positions of the whole step."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    out = {"region_counts": np.array(eng.counts(), np.float64)}
+    if sites is not None:
+        eng.fetch_result()
+        pick = np.sort(rng.choice(len(sites), min(DUMP_SITES, len(sites)), replace=False))
+        lines = []
+        for i in pick:
+            sp = int(sites[i]); d = int(site_vbeg0[i]) + 1 - sp
+            lines.append(np.frombuffer(eng.format_window("chrS", sp - 1 + d, sp + d, d), np.uint8))
+        out["site_index"] = pick.astype(np.float64)
+        out["site_text_len"] = np.array([len(t) for t in lines], np.float64)
+        out["site_text"] = np.concatenate(lines + [np.zeros(0, np.uint8)]).astype(np.float32)
+    else:
+        W = min(DUMP_WINDOW_LEN, region_len)
+        nblk = region_len // W if W > 0 else 0
+        starts = np.sort(rng.choice(nblk, min(DUMP_WINDOWS, nblk), replace=False)) * W if nblk else np.zeros(0, np.int64)
+        L, N = n_lib, len(starts) * W
+        planes = {"ncol": np.zeros((L, N)), "depth": np.zeros((L, N)), "istat": np.zeros((L, capi.NBUCKET, capi.NI, N)),
+                  "fstat": np.zeros((L, capi.NBUCKET, capi.NF, N), np.float32), "refbase": np.zeros(N, np.float32)}
+        ev = np.zeros(len(starts)); keys, ist, fst, alle = [], [], [], []
+        for j, a in enumerate(starts.tolist()):
+            r = eng.fetch_window(a, a + W)
+            ev[j] = r.n_events
+            off = a - r.pos0; n = max(0, min(W, r.n_pos - off)) if off >= 0 else 0   # (planes begin at the lead position a - 1)
+            dst = slice(j * W, j * W + n)
+            for k in ("ncol", "depth", "istat", "fstat"):
+                planes[k][..., dst] = getattr(r, k)[..., off:off + n]
+            if r.unavail is not None:                                      # (per-library mode only)
+                planes.setdefault("unavail", np.zeros(N))[dst] = r.unavail[off:off + n]
+            planes["refbase"][dst] = np.frombuffer(r.refbase, np.uint8)[off:off + n]
+            for x in r.indels:
+                keys.append((x["pos"], x["lib"], x["len"], x["rep_read"], x["rep_qpos"])); ist.append(x["i"]); fst.append(x["f"])
+                alle.append(np.frombuffer(x["allele"].encode("latin1"), np.uint8))
+        out.update(planes, window_start=starts.astype(np.float64), window_events=ev,
+                   indel_key=np.array(keys, np.float64).reshape(-1, 5), indel_istat=np.array(ist, np.float64).reshape(-1, capi.NI),
+                   indel_fstat=np.array(fst, np.float32).reshape(-1, capi.NF), indel_allele=np.concatenate(alle + [np.zeros(0, np.uint8)]).astype(np.float32))
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    for k, v in out.items():
+        assert v.dtype in (np.float32, np.float64), k
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), v)
+    return total
+
+
+def summary_of(rec):
+    """What the result line keeps of a sub-run's record (other_configs, e2e_sites, ...): its scalar fields, the verdicts of its
+    validation and an error; the whole record is printed to stderr (a line of tens of kilobytes is cut short by readers that
+    keep the end of the output)."""
+    if not isinstance(rec, dict):
+        return rec
+    keep = {k: v for k, v in rec.items() if v is None or isinstance(v, (bool, int, float)) or (isinstance(v, str) and len(v) <= 40)}
+    if isinstance(rec.get("validated"), dict):
+        keep["validated"] = {k: v for k, v in rec["validated"].items() if isinstance(v, bool)}
+    if isinstance(rec.get("error"), str):
+        keep["error"] = rec["error"][-300:]
+    return keep
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -133,10 +204,14 @@ def main():
     ap.add_argument("--rank-check-mbp", type=float, default=1.5, help="every rank validates this prefix of ITS OWN interval against the oracle after the timed region (an N-rank run, or --force-dist; "
                     "sites mode: 100 of the rank's own sites); 0 = skip")
     ap.add_argument("--e2e-tumor-mbp", type=float, default=0.0, help="e2e_tumor: the region's contig (0: 6.25 Mbp per rank, at most 25)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed (a fixed, seeded sample: "
+                    "windows of the region, sites of the list) as DIR/<name>.npy in float32 / float64, at most 64 MB")
     ap.add_argument("--dry-run-lib", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--as-rank", type=int, default=None, help=argparse.SUPPRESS)     # with --as-world: one rank's share, without a launcher
     ap.add_argument("--as-world", type=int, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     config = args.config or ("tumor200x" if args.mode == "strong" else "wgs30x")
 
     # ---- N > 1 without a launcher: become `python -m torch.distributed.run ... bench.py <same arguments>`
@@ -255,6 +330,10 @@ def main():
     # (regions of reads with many CIGAR segments: the tile ranges are compacted before the pileup — what they held, what was walked)
     ps = eng.piece_steps() if hasattr(eng.L.lib, "brc_region_piece_steps") else (0, 0)
     piece_steps = {"in_tile_ranges": ps[0], "walked": ps[1], "dead_share_without_compaction": round(1.0 - ps[1] / ps[0], 4)} if ps[0] else None
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(np, capi, eng, args.dump_outputs, "" if world == 1 else "_rank%d" % rank, len(names) if per_lib else 1, region_len,
+                              *((sites, site_vbeg0) if args.mode == "sites" else ()))
     if args.mode == "sites":
         n_events, n_positions = site_events, len(sites)      # the unit of work counts the requested sites only
 
@@ -683,6 +762,12 @@ def main():
             "roofline": roof, "cpu_baseline": cpu, "e2e": e2e, "e2e_sites": e2e_sites, "e2e_tumor": e2e_tumor, "e2e_sharded": e2e_sharded, "abi_roundtrip": abi, "validated": validated, "other_configs": other,
             "host": {"gen_s": round(t_gen, 2), "push_s": round(t_push, 2), "upload_s": round(t_up, 2), "timed_s": round(tmax, 3)},
         }
+        if dumped is not None:
+            line["dump_outputs"] = {"dir": args.dump_outputs, "bytes": int(dumped)}
+        # the whole record to stderr; the result line keeps the scalar fields of other_configs' and e2e_sites' / e2e_tumor's records
+        sys.stderr.write("bench.py: whole record: %s\n" % json.dumps(line)); sys.stderr.flush()
+        line["other_configs"] = {k: summary_of(v) for k, v in other.items()} if other else other
+        line["e2e_sites"], line["e2e_tumor"] = summary_of(e2e_sites), summary_of(e2e_tumor)
         print(json.dumps(line))
     if eng is not None:
         eng.close()

@@ -76,3 +76,51 @@ def test_two_ranks_reduce_what_each_rank_owns(mode):
         for o in own:
             assert 59_000 < o["own_positions"] <= 60_000
         assert own[0]["own_events"] != own[1]["own_events"]                  # different contigs (seed per rank)
+
+
+@pytest.mark.parametrize("mode", ["weak", "strong"])
+def test_dump_outputs_are_reproducible_and_equal_the_oracle(mode, tmp_path, oracle_lib):
+    """--dump-outputs: float32 / float64 arrays, at most 64 MB, the same on every run with the same inputs whatever --steps is,
+    and the sampled windows' planes and indel buckets are what the oracle computes for those windows as regions of their own."""
+    import numpy as np
+    import bench
+    import parity
+    import synthgen
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "sim")])
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    dirs, lines = [], []
+    assert COMMON[:2] == ["--steps", "1"]
+    for steps in ("1", "3"):
+        d = tmp_path / ("steps" + steps)
+        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + MODES[mode] + ["--steps", steps] + COMMON[2:] + ["--dump-outputs", str(d)],
+                             stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
+        assert run.returncode == 0, run.stderr.decode()[-2000:]
+        dirs.append(d); lines.append(line_of(run.stdout))
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1])) and "ncol.npy" in names and "istat.npy" in names
+    got = {n[:-4]: np.load(dirs[0] / n) for n in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    for n in names:
+        np.testing.assert_array_equal(got[n[:-4]], np.load(dirs[1] / n), err_msg=n)
+    assert list(got["region_counts"]) == [lines[0]["own_events"], lines[0]["own_positions"]]
+    assert got["ncol"].sum() == got["window_events"].sum() > 0
+    # the first windows of the sample against the oracle, each as a region of its own
+    per_lib = mode == "strong"
+    contig_len = int(float(MODES[mode][-1]) * 1e6)
+    ref, arrs = synthgen.generate(contig_len, "tumor200x" if per_lib else "wgs30x", seed=1)
+    names_l = ["lib%d" % i for i in range(synthgen.CONFIGS["tumor200x"]["n_libs"])] if per_lib else ()
+    opts = dict(min_mapq=0, min_bq=0, per_lib=True, insertion_centric=True) if per_lib else dict(min_mapq=20, min_bq=13)
+    W = bench.DUMP_WINDOW_LEN
+    n_ind = 0
+    for j, a in enumerate(got["window_start"][:4].astype(int).tolist()):
+        _, (r,) = parity.run_engine(oracle_lib, arrs, [(a, a + W)], ref=ref, lib_names=names_l, **opts)
+        off = a - r.pos0
+        blk = slice(j * W, (j + 1) * W)
+        for k in ("ncol", "depth", "istat"):
+            np.testing.assert_array_equal(got[k][..., blk], getattr(r, k)[..., off:off + W].astype(np.float64), err_msg=k)
+        np.testing.assert_array_equal(got["fstat"][..., blk].view(np.uint32), r.fstat[..., off:off + W].view(np.uint32))
+        want = np.array([(x["pos"], x["lib"], x["len"]) for x in r.indels], np.float64).reshape(-1, 3)
+        np.testing.assert_array_equal(got["indel_key"][n_ind:n_ind + len(want), :3], want)
+        np.testing.assert_array_equal(got["indel_istat"][n_ind:n_ind + len(want)], np.array([x["i"] for x in r.indels], np.float64).reshape(-1, 9))
+        n_ind += len(want)

@@ -1,6 +1,6 @@
 """Inputs of tools/gpu_r5_cram_e2e.sh: <Mbp> of the wgs30x model as syn.bam, syn.fa and (tools/cramio.py, ~110 us per read) syn.cram + .crai, in the current directory."""
 import sys, os, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tools')
+HERE = os.path.dirname(os.path.abspath(__file__)); sys.path.insert(0, os.path.dirname(HERE)); sys.path.insert(0, HERE)
 import numpy as np, synthgen, cramio
 n = int(float(sys.argv[1]) * 1e6)
 ref, a = synthgen.generate(n, "wgs30x", seed=3)

@@ -1,5 +1,5 @@
 import os, sys, subprocess
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 code = r'''
 import os, sys
 sys.path.insert(0, "%s"); sys.path.insert(0, "%s/tools")
