@@ -481,3 +481,85 @@ def kernel_object_hash(path=None):
         if d[stroff + name:end] == b".hip_fatbin":
             return hashlib.sha256(d[off:off + size]).hexdigest()[:16]
     return None
+
+
+# ---------------------------------------------------------------- the BGZF inflater (include/brc_inflate.h)
+INFLATE_LIB = os.path.join(HERE, "csrc", "libbrc_inflate_hip.so")
+INFLATE_EXPORTS = [
+    "brc_inflater_create", "brc_inflater_destroy", "brc_inflater_kind", "brc_inflater_last_error", "brc_inflate_bgzf",
+    "brc_inflate_host_alloc", "brc_inflate_host_free", "brc_inflater_last_timing",
+]
+INF_OK, INF_BAD_HEADER, INF_BAD_STREAM, INF_SIZE_MISMATCH, INF_CRC_MISMATCH, INF_TRUNCATED = range(6)
+E_ARG, E_NODEVICE = -1, -2
+
+
+class Inflater:
+    """One inflater handle of a library exporting include/brc_inflate.h: the product's libbrc_inflate_hip.so (default; raises when it
+    is not built or there is no device — nothing falls back) or the CPU build of the same decoder (tests/sim_inflate)."""
+
+    def __init__(self, path=None, device=0):
+        path = path or INFLATE_LIB
+        if not os.path.exists(path):
+            raise BrcError("inflater library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
+        self.path = path
+        self.lib = L = C.CDLL(path)
+        L.brc_inflater_kind.restype = C.c_char_p
+        L.brc_inflater_last_error.restype = C.c_char_p; L.brc_inflater_last_error.argtypes = [C.c_void_p]
+        L.brc_inflater_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.brc_inflater_destroy.argtypes = [C.c_void_p]; L.brc_inflater_destroy.restype = None
+        L.brc_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+        L.brc_inflate_host_alloc.restype = C.c_void_p; L.brc_inflate_host_alloc.argtypes = [C.c_size_t]
+        L.brc_inflate_host_free.restype = None; L.brc_inflate_host_free.argtypes = [C.c_void_p]
+        L.brc_inflater_last_timing.restype = None
+        L.brc_inflater_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        h = C.c_void_p()
+        rc = L.brc_inflater_create(device, C.byref(h))
+        if rc != 0:
+            raise BrcError("brc_inflater_create failed: %d" % rc)
+        self.h = h
+
+    def kind(self):
+        return self.lib.brc_inflater_kind().decode()
+
+    def close(self):
+        if self.h:
+            self.lib.brc_inflater_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def inflate_raw(self, src, dst_cap=None, capacity=None):
+        """brc_inflate_bgzf as it is: (rc, bytes of dst, dst_off[0..n], statuses[0..n)).  dst_cap / capacity None: sized by a first,
+        size-only call.  dst is pre-filled with 0xA5 (what a failed member's slot must still hold afterwards)."""
+        src = bytes(src)
+        sbuf = np.frombuffer(src, np.uint8) if src else np.zeros(1, np.uint8)
+        cap = len(src) // 26 + 1 if capacity is None else capacity
+        off = np.zeros(cap + 1, np.uint64); st = np.zeros(max(cap, 1), np.uint8)
+        n = C.c_size_t(cap)
+        if dst_cap is None:
+            self.lib.brc_inflate_bgzf(self.h, sbuf.ctypes.data, len(src), None, 0, off.ctypes.data, st.ctypes.data, C.byref(n))
+            dst_cap = int(off[n.value]) if n.value <= cap else 0
+            n = C.c_size_t(cap)
+        dst = np.full(max(dst_cap, 1), 0xA5, np.uint8)
+        rc = self.lib.brc_inflate_bgzf(self.h, sbuf.ctypes.data, len(src), dst.ctypes.data, dst_cap, off.ctypes.data, st.ctypes.data, C.byref(n))
+        k = n.value
+        if k > cap:
+            return rc, b"", np.zeros(0, np.uint64), np.zeros(0, np.uint8), k
+        return rc, dst[:min(dst_cap, int(off[k]))].tobytes(), off[:k + 1].copy(), st[:k].copy(), k
+
+    def inflate(self, src):
+        """Raw BGZF bytes (whole members back to back) -> (inflated bytes, offsets (n + 1), statuses (n)).  Raises when src is not a
+        chain of whole members; members that failed are reported by their status, their bytes are not meaningful."""
+        rc, out, off, st, _ = self.inflate_raw(src)
+        if rc != 0:
+            raise BrcError("brc_inflate_bgzf: %d (%s)" % (rc, self.lib.brc_inflater_last_error(self.h).decode()))
+        return out, off, st
+
+    def last_timing(self):
+        k = C.c_double(); c = C.c_double(); bi = C.c_uint64(); bo = C.c_uint64()
+        self.lib.brc_inflater_last_timing(self.h, C.byref(k), C.byref(c), C.byref(bi), C.byref(bo))
+        return dict(kernel_s=k.value, call_s=c.value, bytes_in=bi.value, bytes_out=bo.value)

@@ -1,5 +1,6 @@
 // bamio.cpp — see bamio.h.  Wire formats per the public SAMv1 specification; no htslib code involved.
 #include "bamio.h"
+#include "../brc_inflate_core.h"
 
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -11,6 +12,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <chrono>
 #include <set>
 
 namespace brcio {
@@ -54,6 +56,7 @@ void Bgzf::close() { if (f_) fclose(f_); f_ = nullptr; if (ld_) { libdeflate().r
 
 // One BGZF member: gzip header with the BC extra subfield (total block size - 1), raw deflate payload, CRC32, ISIZE.
 bool Bgzf::load_block(uint64_t coff) {
+    if (ext_) return load_block_external(coff);
     if (fseeko(f_, (off_t)coff, SEEK_SET) != 0) { err_ = "seek failed"; return false; }
     uint8_t h[18];
     const size_t got = fread(h, 1, 18, f_);
@@ -94,8 +97,105 @@ bool Bgzf::load_block(uint64_t coff) {
         crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), ubuf_.data(), (uInt)isize);
     }
     if (crc != rd32(tail)) { err_ = "BGZF block CRC32 mismatch"; return false; }
-    block_coff_ = coff; next_coff_ = coff + (uint64_t)bsize + 1; len_ = isize; pos_ = 0;
+    block_coff_ = coff; next_coff_ = coff + (uint64_t)bsize + 1; len_ = isize; pos_ = 0; cur_ = ubuf_.data();
     return true;
+}
+
+// ---- blocks through an external inflater
+const InflatedWindow::Mem* InflatedWindow::find(uint64_t coff) const {
+    auto it = std::lower_bound(mem.begin(), mem.end(), coff, [](const Mem& m, uint64_t c) { return m.coff < c; });
+    return it != mem.end() && it->coff == coff ? &*it : nullptr;
+}
+
+// The same walk as load_block's, over bytes read ahead: where that would have failed (or met the end of the file) the window keeps
+// the answer as its last entry of the range; a member the bytes read ahead do not hold whole is left to a later, on-demand window.
+std::shared_ptr<InflatedWindow> Bgzf::build_window(const std::vector<std::pair<uint64_t, uint64_t> >& ranges) {
+    std::shared_ptr<InflatedWindow> w(new InflatedWindow());
+    if (!f_ || !ext_) return w;
+    size_t want = 0;
+    for (const auto& r : ranges) want += (size_t)(r.second - r.first) + (2u << 16);
+    std::unique_ptr<uint8_t, void (*)(void*)> src((uint8_t*)malloc(want ? want : 1), free);
+    if (!src) return w;
+    size_t fill = 0; uint64_t out = 0; size_t n_real = 0;
+    for (const auto& r : ranges) {
+        if (fseeko(f_, (off_t)r.first, SEEK_SET) != 0) continue;
+        const size_t ask = (size_t)(r.second - r.first) + (2u << 16);
+        const size_t got = fread(src.get() + fill, 1, ask, f_);
+        const bool at_eof = got < ask;
+        const uint8_t* p = src.get() + fill;
+        size_t o = 0;
+        auto stop = [&](uint8_t kind, const char* m) { InflatedWindow::Mem e; e.coff = r.first + o; e.total = 0; e.isize = 0; e.off = 0; e.status = 0; e.kind = kind; w->mem.push_back(e); if (m) w->msg = m; };
+        while (r.first + o <= r.second && w->msg.empty()) {
+            const size_t left = got - o;
+            if (left == 0) { if (at_eof) stop(1, nullptr); break; }
+            // one header walk for the inflater and for this file (brcinf::member_header); what is kept here is load_block's wording:
+            // 1 = magic / FEXTRA / no BC subfield, 2 = the bytes end inside the header
+            const uint8_t* h = p + o;
+            uint32_t total32 = 0, hdr = 0;
+            const int hrc = brcinf::member_header(h, left, &total32, &hdr);
+            if (hrc == 2) { if (at_eof) stop(2, left < 18 ? "not a BGZF block" : "truncated BGZF header"); break; }
+            if (hrc == 1) { stop(2, (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) ? "not a BGZF block" : "BGZF block without BC subfield"); break; }
+            const size_t total = total32;
+            if (total < hdr + 8u || left < total) { if (at_eof || total < hdr + 8u) stop(2, "truncated BGZF block"); break; }
+            InflatedWindow::Mem e; e.coff = r.first + o; e.total = (uint32_t)total; e.isize = rd32(h + total - 4); e.off = out; e.status = 0; e.kind = 0;
+            if (e.isize > (1u << 16)) { e.status = 1; e.isize = 0; }      // (the inflater gives such a member no room either)
+            out += e.isize; w->mem.push_back(e); ++n_real;
+            o += total;
+        }
+        // keep the whole members only: the next range's bytes follow them
+        size_t keep = 0; for (size_t k = w->mem.size(); k-- > 0 && w->mem[k].coff >= r.first;) if (w->mem[k].kind == 0) keep += w->mem[k].total;
+        fill += keep;
+        if (!w->msg.empty()) break;          // (one error entry per window: what lies behind it is read when a reader gets there)
+    }
+    if (n_real) {
+        w->data.reset((uint8_t*)malloc(out ? (size_t)out : 1));
+        std::vector<uint64_t> off(n_real + 1); std::vector<uint8_t> st(n_real);
+        size_t n = n_real;
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = w->data ? ext_->inflate(ext_->handle, src.get(), fill, w->data.get(), (size_t)out, off.data(), st.data(), &n) : -4;
+        ext_->nanos += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+        ext_->bytes_in += fill; ext_->bytes_out += out; ext_->calls += 1;
+        size_t k = 0;
+        for (InflatedWindow::Mem& e : w->mem) {
+            if (e.kind != 0) continue;
+            if (rc != 0 || n != n_real || off[k] != e.off) e.status = 255;      // the call itself failed: every member says so when it is reached
+            else e.status = st[k];
+            ++k;
+        }
+    }
+    std::sort(w->mem.begin(), w->mem.end(), [](const InflatedWindow::Mem& a, const InflatedWindow::Mem& b) { return a.coff < b.coff; });
+    return w;
+}
+
+bool Bgzf::load_block_external(uint64_t coff) {
+    const InflatedWindow* w = nullptr; const InflatedWindow::Mem* m = nullptr;
+    if (shared_ && (m = shared_->find(coff))) w = shared_.get();
+    else if (own_ && (m = own_->find(coff))) w = own_.get();
+    else {
+        // outside every window: the next stretch of the file from here (a record that runs past a chunk's last block, a query
+        // nobody prefetched for — the site-list fetches —, the header)
+        static const uint64_t span = 256 << 10;
+        own_ = build_window(std::vector<std::pair<uint64_t, uint64_t> >(1, std::make_pair(coff, coff + span)));
+        if (!(m = own_->find(coff))) { err_ = "seek failed"; return false; }
+        w = own_.get();
+    }
+    if (m->kind == 1) { eof_ = true; len_ = pos_ = 0; block_coff_ = coff; next_coff_ = coff; return false; }
+    if (m->kind == 2) { err_ = w->msg; return false; }
+    if (m->status != 0) { err_ = m->status == 4 ? "BGZF block CRC32 mismatch" : "inflate failed"; return false; }
+    cur_ = w->data.get() + m->off;
+    block_coff_ = coff; next_coff_ = coff + m->total; len_ = m->isize; pos_ = 0;
+    return true;
+}
+
+std::shared_ptr<InflatedWindow> BamReader::prefetch(const BamIndex& idx, int tid, int64_t beg, int64_t end) {
+    if (beg < 0) beg = 0;
+    std::vector<std::pair<uint64_t, uint64_t> > ranges;
+    if (end > beg) for (const Chunk& c : idx.query(tid, beg, end)) {
+        const uint64_t a = c.beg >> 16, b = c.end >> 16;
+        if (!ranges.empty() && a <= ranges.back().second) { if (b > ranges.back().second) ranges.back().second = b; }
+        else ranges.push_back(std::make_pair(a, b));
+    }
+    return bg_.build_window(ranges);
 }
 
 bool Bgzf::seek(uint64_t voffset) {
@@ -115,7 +215,7 @@ bool Bgzf::read(void* dst, size_t n) {
             do { if (!load_block(next_coff_)) return false; } while (len_ == 0);
         }
         const size_t k = std::min(n, len_ - pos_);
-        memcpy(d, ubuf_.data() + pos_, k);
+        memcpy(d, cur_ + pos_, k);
         pos_ += k; d += k; n -= k;
     }
     return true;
@@ -126,7 +226,7 @@ size_t Bgzf::read_some(void* dst, size_t n) {
     while (got < n) {
         if (pos_ == len_) { bool ok = true; do { ok = load_block(next_coff_); } while (ok && len_ == 0); if (!ok) break; }
         const size_t k = std::min(n - got, len_ - pos_);
-        memcpy(d + got, ubuf_.data() + pos_, k);
+        memcpy(d + got, cur_ + pos_, k);
         pos_ += k; got += k;
     }
     return got;

@@ -10,16 +10,47 @@
 
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
+#include <atomic>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace brcio {
 
 // ---------------------------------------------------------------- BGZF
+// An inflater outside this file (include/brc_inflate.h, reached through pointers: the command line finds the library with dlopen, so
+// nothing new is linked): many members per call instead of one.  Shared by every handle of a process; the account is for BRC_CLI_TIMING.
+struct ExtInflater {
+    void* handle = nullptr;
+    int (*inflate)(void*, const void*, size_t, void*, size_t, uint64_t*, uint8_t*, size_t*) = nullptr;      // brc_inflate_bgzf
+    void (*destroy)(void*) = nullptr;                                                                        // brc_inflater_destroy
+    std::atomic<uint64_t> bytes_in{0}, bytes_out{0}, nanos{0}, calls{0};
+};
+
+// Members of a file inflated ahead, by their compressed offsets.  Immutable once built: the stripes of a piece read one window side
+// by side.  A member keeps what loading it would have answered (its bytes, an inflate / CRC failure, a broken header, the end of
+// the file): the answer is given when a reader ARRIVES at the member, exactly where block-by-block reading would have met it —
+// a damaged block behind the last record a query needs stays unnoticed, as it does there.
+struct InflatedWindow {
+    struct Mem { uint64_t coff; uint32_t total, isize; uint64_t off; uint8_t status; uint8_t kind; };      // kind 0: member, 1: end of file, 2: error `msg`
+    std::vector<Mem> mem;            // sorted by coff
+    std::unique_ptr<uint8_t, void (*)(void*)> data{nullptr, free};
+    std::string msg;                 // of the one kind-2 entry
+    const Mem* find(uint64_t coff) const;
+};
+
 class Bgzf {
   public:
+    // from now on blocks come from windows inflated by `e` (nullptr: this handle's own inflate, one block at a time)
+    void set_external(ExtInflater* e) { ext_ = e; own_.reset(); shared_.reset(); len_ = pos_ = 0; }
+    // a window built ahead for this handle and others (build_window); blocks outside it are inflated on demand, a smaller window at a time
+    void share_window(std::shared_ptr<const InflatedWindow> w) { shared_ = std::move(w); len_ = pos_ = 0; }
+    // the members that start in the compressed ranges [beg, end] (sorted, disjoint), read and inflated in one call
+    std::shared_ptr<InflatedWindow> build_window(const std::vector<std::pair<uint64_t, uint64_t> >& ranges);
+    bool external() const { return ext_ != nullptr; }
     bool open(const std::string& path);
     void close();
     ~Bgzf() { close(); }
@@ -34,6 +65,10 @@ class Bgzf {
 
   private:
     bool load_block(uint64_t coff);
+    bool load_block_external(uint64_t coff);
+    ExtInflater* ext_ = nullptr;
+    std::shared_ptr<const InflatedWindow> shared_, own_;
+    const uint8_t* cur_ = nullptr;   // the current block's bytes (ubuf_, or inside a window)
     FILE* f_ = nullptr;
     std::vector<uint8_t> cbuf_, ubuf_;
     uint64_t block_coff_ = 0, next_coff_ = 0;
@@ -128,6 +163,13 @@ class BamReader {
         return true;
     }
     const std::string& error() const { return err_; }
+    // Reading through an external inflater (Bgzf::set_external).  prefetch: one window over everything a fetch of [beg, end) on tid
+    // may read — the compressed ranges of the index's chunks, whole — for share_window of this reader and of others that read parts
+    // of the same query; fetch() itself is unchanged, virtual offsets and chunk ends mean what they meant.
+    void set_external(ExtInflater* e) { bg_.set_external(e); }
+    bool external() const { return bg_.external(); }
+    void share_window(std::shared_ptr<const InflatedWindow> w) { bg_.share_window(std::move(w)); }
+    std::shared_ptr<InflatedWindow> prefetch(const BamIndex& idx, int tid, int64_t beg, int64_t end);
 
   private:
     Bgzf bg_;

@@ -19,6 +19,12 @@
 // the HIP runtime; rank r binds to GPU devices[r] and to its share of the CPUs, takes a contiguous, event-weighted slice of the
 // work list IN FILE ORDER (the rule of shard.partition; weights from the index's file offsets, BamIndex::span_bytes) and prints
 // it; the coordinating process writes the ranks' text and stderr in rank order — see "ranks" below.
+//
+// --brc-device-inflate (BRC_DEVICE_INFLATE=1; off by default): the BGZF blocks of a BAM are inflated on the GPU, a piece's worth per
+// call, by the inflater library of include/brc_inflate.h — found with dlopen (BRC_INFLATE_LIB, else libbrc_inflate_hip.so next to
+// this executable; a missing library or device is an error, exit code 1) — instead of one block at a time on the fetch threads.
+// Output, messages and exit codes are those of the switch off.  Every rank opens its own inflater on its own GPU; CRAM input has no
+// BGZF blocks and says once that the switch is ignored.
 #include <errno.h>
 #include <limits.h>
 #include <stdio.h>
@@ -52,6 +58,7 @@ struct Options {
     long long streams = 0;          // engines per GPU (0: one; every engine already overlaps decode | GPU | format of consecutive pieces): --brc-streams
     long long ranks = 0;            // processes, one per GPU: --brc-ranks (BRC_RANKS)
     std::string rank_of;            // "r:N": this process IS rank r of N (what the coordinating process starts its children with): --brc-rank-of
+    bool device_inflate = false;    // BGZF blocks inflated by the inflater library (include/brc_inflate.h): --brc-device-inflate (BRC_DEVICE_INFLATE=1)
     std::string tmpdir;             // where the ranks behind the first keep their text until its turn comes: --brc-tmpdir (TMPDIR, /tmp)
 };
 
@@ -85,7 +92,7 @@ static const OptSpec kSpecs[] = {
     {'h', "help", false}, {'v', "version", false}, {'q', "min-mapping-quality", true}, {'b', "min-base-quality", true},
     {'d', "max-count", true}, {'l', "site-list", true}, {'f', "reference-fasta", true}, {'D', "print-individual-mapq", true},
     {'p', "per-library", false}, {'w', "max-warnings", true}, {'i', "insertion-centric", false}, {0, "brc-chunk", true}, {1, "brc-plan", true}, {2, "brc-gpus", true}, {3, "brc-streams", true},
-    {4, "brc-ranks", true}, {5, "brc-rank-of", true}, {6, "brc-tmpdir", true},
+    {4, "brc-ranks", true}, {5, "brc-rank-of", true}, {6, "brc-tmpdir", true}, {7, "brc-device-inflate", false},
 };
 
 static bool apply(Options& o, const OptSpec& sp, const std::string& v, std::string* err) {
@@ -117,6 +124,7 @@ static bool apply(Options& o, const OptSpec& sp, const std::string& v, std::stri
         case 4: if (!to_ll(&x)) return false; o.ranks = x; return true;
         case 5: o.rank_of = v; return true;
         case 6: o.tmpdir = v; return true;
+        case 7: o.device_inflate = true; return true;
         default: if (!to_ll(&x)) return false; o.chunk_bp = x; o.chunk_given = true; return true;
     }
 }
@@ -325,6 +333,7 @@ struct Ctx {
     CramReader cram; bool is_cram = false;          // CRAM 3.0 input (cram.cpp); region queries go through the .crai or one walk over the container headers
     const BamHeader& header() const { return is_cram ? cram.header() : bam.header(); }
     brc_engine* eng = nullptr;
+    ExtInflater* inf = nullptr;             // --brc-device-inflate: this context's inflater (its GPU's); destroyed on the orderly exit path (BRC_CLEAN_EXIT)
     std::vector<std::string> libs;
     int ref_tid = -1; std::string ref;      // currently loaded contig (load_reference, :83-90)
     Batcher batch;
@@ -426,6 +435,14 @@ static void fetch_chunk(Ctx& c, int tid, int64_t a, int64_t b, Fetched& out) {
         return;
     }
     while (out.pool.size() < K) { out.pool.emplace_back(new BamReader()); if (!out.pool.back()->open(c.opt.bam)) { out.ok = false; out.err = "cannot reopen " + c.opt.bam; return; } }
+    // --brc-device-inflate: everything the piece's query may read is inflated in one call; the stripes read that window side by side
+    // (a block outside it — a record that runs past a chunk's last block — is inflated on demand by the stripe that needs it)
+    if (c.inf) {
+        for (unsigned i = 0; i < K; ++i) if (!out.pool[i]->external()) out.pool[i]->set_external(c.inf);
+        std::shared_ptr<InflatedWindow> w = out.pool[0]->prefetch(c.idx, tid, a - 1, b);
+        for (unsigned i = 0; i < K; ++i) out.pool[i]->share_window(w);
+    }
+    struct DropWindow { Fetched& f; ~DropWindow() { for (auto& r : f.pool) if (r->external()) r->share_window(nullptr); } } drop_window{out};
     std::atomic<int> failed(0);
     auto work = [&](unsigned i) {
         const int64_t s0 = q0 + (b - q0) * (int64_t)i / (int64_t)K, s1 = q0 + (b - q0) * (int64_t)(i + 1) / (int64_t)K;
@@ -617,6 +634,7 @@ static void fetch_site_batch(const Ctx& c, const std::vector<Site>& sites, SiteF
     auto work = [&]() {
         BamReader rd;
         if (!rd.open(c.opt.bam)) { failed = 1; return; }
+        if (c.inf) rd.set_external(c.inf);
         for (;;) {
             const size_t ci = next.fetch_add(1);
             if (ci >= clusters.size()) break;
@@ -868,6 +886,37 @@ static int make_engine(Ctx& c, int device) {
     if (rc == 0 && g_format_threads.load()) brc_set_option(c.eng, BRC_OPT_FORMAT_THREADS, (int64_t)g_format_threads.load());
     if (rc == 0 && o.max_cnt <= 0) brc_set_option(c.eng, BRC_OPT_MAX_COUNT, o.max_cnt);   // -d 0 / -d -3 reach the iterator as they are (:592,:651)
     return rc;
+}
+
+// --brc-device-inflate: the inflater library through dlopen (nothing of it is linked: the simulator's command line is this very file).
+// A missing library, entry point or device ends the run — there is no quiet return to the host path.
+#include <dlfcn.h>
+static int open_inflater(Ctx& c, int device) {
+    static std::mutex mu; std::lock_guard<std::mutex> g(mu);
+    static void* lib = nullptr; static std::string path;
+    typedef int (*create_fn)(int, void**);
+    if (!lib) {
+        if (const char* e = getenv("BRC_INFLATE_LIB")) path = e;
+        else {
+            char exe[PATH_MAX]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
+            path = n > 0 ? std::string(exe, (size_t)n) : std::string("bam-readcount");
+            const size_t sl = path.rfind('/');
+            path = (sl == std::string::npos ? std::string(".") : path.substr(0, sl)) + "/libbrc_inflate_hip.so";
+        }
+        lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!lib) { fprintf(stderr, "bam-readcount: --brc-device-inflate: cannot load the inflater library %s: %s\n", path.c_str(), dlerror()); return 1; }
+    }
+    create_fn create = (create_fn)dlsym(lib, "brc_inflater_create");
+    void* fn = dlsym(lib, "brc_inflate_bgzf");
+    if (!create || !fn) { fprintf(stderr, "bam-readcount: --brc-device-inflate: %s does not export the inflater of include/brc_inflate.h\n", path.c_str()); return 1; }
+    void* h = nullptr;
+    const int rc = create(device, &h);
+    if (rc != 0 || !h) { fprintf(stderr, "bam-readcount: --brc-device-inflate: cannot create an inflater on device %d: %s\n", device, brc_strerror(rc)); return 1; }
+    c.inf = new ExtInflater();
+    c.inf->handle = h;
+    c.inf->destroy = (void (*)(void*))dlsym(lib, "brc_inflater_destroy");
+    c.inf->inflate = (int (*)(void*, const void*, size_t, void*, size_t, uint64_t*, uint8_t*, size_t*))fn;
+    return 0;
 }
 
 // A crash must not be silent: frames of the faulting thread (module + offset: `addr2line -e <module> <offset>` resolves
@@ -1168,6 +1217,15 @@ int main(int argc, char** argv) {
     // in order.  (One region — a chromosome — and site lists spread over the engines.)
     if (o.site_list.empty() && o.regions.size() > 1) devices.resize(1);
     size_t N = devices.size();
+    if (!o.device_inflate && getenv("BRC_DEVICE_INFLATE") && atoi(getenv("BRC_DEVICE_INFLATE")) != 0) c.opt.device_inflate = true;
+    if (c.opt.device_inflate) {
+        if (c.is_cram) { c.opt.device_inflate = false; if (lead) fprintf(stderr, "bam-readcount: --brc-device-inflate is ignored for CRAM input\n"); }
+    }
+    // (like the engine below: the inflater starts the HIP runtime on a thread of its own while this one reads the index and the site list;
+    // the work items wait for it)
+    std::thread inf_thread; int inf_rc = 0;
+    if (c.opt.device_inflate) inf_thread = std::thread([&]() { inf_rc = open_inflater(c, devices[0]); });
+    struct JoinInf { std::thread& t; ~JoinInf() { if (t.joinable()) t.join(); } } join_inf{inf_thread};
     // The engine (HIP runtime start, streams) is created on a thread of its own while this one reads the index and the site
     // list and — inside the first work item — the reference and the first reads; whoever needs the engine waits for it.
     double t_engine0 = 0;
@@ -1303,6 +1361,7 @@ int main(int argc, char** argv) {
         }
     }
 
+    if (inf_thread.joinable()) { inf_thread.join(); if (inf_rc != 0) return leave(1); }      // no reader starts before the inflater exists (or the run ends: no return to the host path)
     if (items.size() < N) N = std::max<size_t>(items.size(), 1);      // engines without work are never created
     if (N > 1) {    // the engines share this process's CPUs: each gets its part of the decode and formatter pools
         g_engines = (unsigned)N;
@@ -1372,7 +1431,7 @@ int main(int argc, char** argv) {
             Ctx* wc = &c;
             if (g > 0) {                                                             // own handles, own engine
                 ctxs[g].reset(new Ctx()); wc = ctxs[g].get(); wc->opt = c.opt;
-                bool ok = open_inputs(*wc, true) && (wc->is_cram || wc->idx.load(c.opt.bam)) && make_engine(*wc, devices[g]) == 0;
+                bool ok = open_inputs(*wc, true) && (wc->is_cram || wc->idx.load(c.opt.bam)) && make_engine(*wc, devices[g]) == 0 && (!c.opt.device_inflate || open_inflater(*wc, devices[g]) == 0);
                 if (!ok) {
                     std::lock_guard<std::mutex> lk(mu);
                     for (Work& w : items) if ((size_t)w.engine == g && !w.done) { w.rc = 1; w.err = "bam-readcount: cannot set up the engine of GPU " + std::to_string(devices[g]) + "\n"; w.done = true; }
@@ -1441,12 +1500,14 @@ int main(int argc, char** argv) {
         { std::lock_guard<std::mutex> lk(mu); abort_all = abort_all || ret != 0; printed = items.size(); cv.notify_all(); }
         for (std::thread& t : th) t.join();
         // (the process is about to end: see below for why the engines are only destroyed on request)
-        for (size_t g = 1; g < N; ++g) if (ctxs[g]) { for (int w = 0; w < BRC_N_WARN; ++w) c.warn[w] += ctxs[g]->warn[w]; if (ctxs[g]->eng && clean_exit) brc_destroy(ctxs[g]->eng); }
+        for (size_t g = 1; g < N; ++g) if (ctxs[g]) { for (int w = 0; w < BRC_N_WARN; ++w) c.warn[w] += ctxs[g]->warn[w]; if (ctxs[g]->eng && clean_exit) brc_destroy(ctxs[g]->eng); if (ctxs[g]->inf && clean_exit) { ctxs[g]->bufs.clear(); ctxs[g]->pf_buf.reset(); if (ctxs[g]->inf->destroy) ctxs[g]->inf->destroy(ctxs[g]->inf->handle); delete ctxs[g]->inf; ctxs[g]->inf = nullptr; } }
         if (!clean_exit) for (auto& p : ctxs) (void)p.release();
     }
     const std::string who = my_rank >= 0 ? "rank " + std::to_string(my_rank) + ": " : std::string();
     if (getenv("BRC_CLI_TIMING")) fprintf(stderr, "%sstartup: open inputs %.3f s, create engine %.3f s\n", who.c_str(), t_inputs - t_start, t_engine0 - t_inputs);
     if (getenv("BRC_CLI_TIMING")) fprintf(stderr, "%stiming: fetch+decode %.3f s, engine (push, upload, kernels, download) %.3f s, format %.3f s, write %.3f s\n", who.c_str(), c.t_fetch, c.t_engine, c.t_format, c.t_write);
+    if (getenv("BRC_CLI_TIMING") && c.inf)
+        fprintf(stderr, "%sdevice inflate: %llu calls, %.1f MB in, %.1f MB out, %.3f s inside the fetch threads\n", who.c_str(), (unsigned long long)c.inf->calls.load(), c.inf->bytes_in.load() / 1e6, c.inf->bytes_out.load() / 1e6, c.inf->nanos.load() * 1e-9);
     if (getenv("BRC_CLI_TIMING") && c.n_site_lines)
         fprintf(stderr, "%ssites: %llu lines in %llu clusters, %llu engine regions of %llu reads all told: waiting for indexed fetch + decode %.3f s (the fetches themselves, next batch behind the current one: %.3f s), layout on the virtual axis %.3f s, engine (push, upload, kernels, download) %.3f s, cutting the lines out + writing %.3f s\n",
                 who.c_str(), (unsigned long long)c.n_site_lines, (unsigned long long)c.n_site_clusters, (unsigned long long)c.n_site_batches, (unsigned long long)c.n_site_reads, c.t_site_fetch, c.t_site_fetch_threads, c.t_site_layout, c.t_site_engine, c.t_site_format);
@@ -1459,5 +1520,6 @@ int main(int argc, char** argv) {
     if (my_rank >= 0 && !clean_exit) { close(1); close(2); }
     if (!clean_exit) _exit(ret);
     if (wait_engine()) brc_destroy(c.eng);
+    if (c.inf) { c.bufs.clear(); c.pf_buf.reset(); if (c.inf->destroy) c.inf->destroy(c.inf->handle); delete c.inf; c.inf = nullptr; }      // (its readers first)
     return ret;
 }

@@ -98,7 +98,7 @@ def timed_to_devnull(cmd, cwd, reps):
         if rc != 0:
             raise SystemExit("command failed (%d): %s\n%s" % (rc, " ".join(cmd), err[-2000:]))
         if best is None or t < best:
-            best, stages = t, [l for l in err.splitlines() if l.startswith(("startup:", "timing:", "sites:", "engine timing", "device buffers"))]
+            best, stages = t, [l for l in err.splitlines() if l.startswith(("startup:", "timing:", "sites:", "device inflate:", "engine timing", "device buffers"))]
     # once more with the engine's own account (BRC_ENGINE_TIMING=1 takes the orderly exit path: not the timed run)
     with open(os.devnull, "wb") as dn:
         _, rc, err = run(cmd, cwd, dn, dict(env, BRC_ENGINE_TIMING="1"))
