@@ -15,10 +15,16 @@ max-over-ranks step time.
                  pipeline once per step.  The genome is scaled: one 50-Mbp contig per rank instead of 3.1 Gbp.
 
 `--gpus N` with N > 1 re-executes itself under torch.distributed.run (one rank per GPU, RCCL) unless it already runs
-under a launcher.  Extra objects on the JSON line:
+under a launcher.
+
+A plain run does what the headline figure needs and nothing else: it generates and uploads the inputs, warms up, times the steps,
+writes --dump-outputs if asked to, and prints the line; `roofline` is arithmetic on the timed steps' own HIP events and on committed
+counter files.  `--full` adds every other measurement and check below, each in a leg of its own after the timed region (minutes of
+oracle and command-line runs); without it their fields are null.  Extra objects on the JSON line:
   roofline      SURVEY 8d's algorithmic bytes (B_in + B_ref + B_out, dense 312 B per position and library) over the WHOLE device step
                 (HIP events on the engine's stream), against the 8 TB/s HBM peak; per_kernel: each of the two big kernels against its OWN
                 bytes and against its PMC traffic (profiles/r06_traffic.json, reported only when stamped with the loaded kernel object)
+  (the rest with --full only)
   cpu_baseline  the C oracle (CPU restatement of the reference semantics): 1 thread like the reference on a prefix, the reference's own
                 sources compiled over a shim (oracle/_ref) on a smaller prefix, and all cores = the whole-region validation below
   e2e           the drop-in command line on a generated BAM + BAI -> /dev/null (BAM decode, PCIe, formatting included)
@@ -206,6 +212,9 @@ def main():
     ap.add_argument("--e2e-tumor-mbp", type=float, default=0.0, help="e2e_tumor: the region's contig (0: 6.25 Mbp per rank, at most 25)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed (a fixed, seeded sample: "
                     "windows of the region, sites of the list) as DIR/<name>.npy in float32 / float64, at most 64 MB")
+    ap.add_argument("--full", action="store_true", help="besides the timed steps, run everything else this script measures or checks: validation against the oracle (prefix, whole region, "
+                    "every rank's own interval), cpu_baseline, e2e, e2e_sites / e2e_tumor / e2e_sharded, abi_roundtrip, other_configs.  Without it a run sets up, warms up, "
+                    "times the steps, writes --dump-outputs and prints the line; the options that size those legs are read only with --full")
     ap.add_argument("--dry-run-lib", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--as-rank", type=int, default=None, help=argparse.SUPPRESS)     # with --as-world: one rank's share, without a launcher
     ap.add_argument("--as-world", type=int, default=None, help=argparse.SUPPRESS)
@@ -237,7 +246,8 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     ncpu = os.cpu_count() or 1
     ncpu_eff = effective_cpus()
-    nworkers = (min(ncpu_eff, 64) if args.cpu_all_cores < 0 else args.cpu_all_cores) if (rank == 0 and world == 1 and args.cpu_sample_mbp > 0) else 0
+    extras = args.full                               # everything beyond set-up, warm-up, the timed steps, --dump-outputs and the line
+    nworkers = (min(ncpu_eff, 64) if args.cpu_all_cores < 0 else args.cpu_all_cores) if (extras and rank == 0 and world == 1 and args.cpu_sample_mbp > 0) else 0
 
     per_lib = config == "tumor200x"
     names = ["lib%d" % i for i in range(synthgen.CONFIGS[config]["n_libs"])] if per_lib else ()
@@ -256,7 +266,7 @@ def main():
     # The oracle processes of the whole-region validation are forked HERE — before this process touches the GPU (a process
     # that has initialised the HIP runtime must not fork); they inherit the reads and sleep until the timed region is over.
     pool = None
-    full_check = args.full_check if args.full_check >= 0 else (1 if (world == 1 and not dry and args.mode != "sites" and args.cpu_sample_mbp > 0 and nworkers > 0) else 0)
+    full_check = 0 if not extras else args.full_check if args.full_check >= 0 else (1 if (world == 1 and not dry and args.mode != "sites" and args.cpu_sample_mbp > 0 and nworkers > 0) else 0)
     if full_check and rank == 0 and world == 1 and not dry and args.mode != "sites":
         import fullcheck
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
@@ -358,7 +368,7 @@ def main():
     # ---- every rank validates a prefix of ITS OWN interval (its own sites) against the oracle, one thread, after the timed region:
     # a wrong result on rank 5 of an 8-GPU run must not print a healthy line.  The verdicts are MIN-reduced.
     rank_check = None
-    if (dist is not None or emulated) and args.rank_check_mbp > 0:
+    if extras and (dist is not None or emulated) and args.rank_check_mbp > 0:
         rank_check = {"ok": 1, "events": 0, "what": "", "error": None}
         try:
             import parity
@@ -516,11 +526,13 @@ def main():
         # ---- validation + 1-thread CPU baseline on a prefix of the timed contig
         cpu = None; validated = None
         ends = capi.read_ends(arrs)
-        if args.mode != "sites":
+        if extras and args.mode != "sites":
             span = int((np.minimum(ends, contig_len) - np.maximum(arrs["pos"].astype(np.int64), 0)).clip(min=0).sum())
             dropped = (arrs["flag"] & 4) != 0
             validated = {"events_equal_sum_of_spans": bool(eng_events == span and not dropped.any())}
-        if args.mode == "sites" and args.cpu_sample_mbp > 0:
+        if not extras:
+            pass
+        elif args.mode == "sites" and args.cpu_sample_mbp > 0:
             # a sample of the site list against the oracle, site by site: the reference's own -l loop (one fetch + pileup per line,
             # bamreadcount.cpp:574-607) vs the line cut out of the shared virtual axis
             subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
@@ -615,7 +627,7 @@ def main():
                                               % (full["events"], full["windows"], npr, ncpu, ncpu_eff)}
         # ---- end to end through the drop-in command line (BAM decode + PCIe + text)
         e2e = None
-        if args.e2e_mbp > 0 and world == 1 and os.path.exists(CLI):
+        if extras and args.e2e_mbp > 0 and world == 1 and os.path.exists(CLI):
             import tempfile
             n = int(args.e2e_mbp * 1e6)
             d = tempfile.mkdtemp(prefix="brc_e2e_")
@@ -652,7 +664,7 @@ def main():
         # (begin -> push -> upload -> compute -> device-side text -> download -> the host's line patches), piece by piece on ONE
         # engine, nothing overlapped (the command line overlaps decode, engine and formatting of consecutive pieces on threads)
         abi = None
-        if args.abi_mbp > 0 and world == 1 and args.mode == "weak" and not per_lib:
+        if extras and args.abi_mbp > 0 and world == 1 and args.mode == "weak" and not per_lib:
             piece = 2_000_000; alen = int(min(args.abi_mbp * 1e6, contig_len))
             cuts = [(a, min(a + piece, alen)) for a in range(0, alen, piece)]
             pos64 = arrs["pos"].astype(np.int64)
@@ -679,7 +691,7 @@ def main():
         # own validation (config 4: 400 sites against one oracle region per site; config-5 shape: planes + text of a prefix
         # against the oracle) runs inside them
         other = None
-        want_other = args.other_configs == 1 or (args.other_configs < 0 and world == 1 and args.mode == "weak" and config == "wgs30x" and abs(args.contig_mbp - 50.0) < 1e-9 and args.cpu_sample_mbp > 0)
+        want_other = extras and (args.other_configs == 1 or (args.other_configs < 0 and world == 1 and args.mode == "weak" and config == "wgs30x" and abs(args.contig_mbp - 50.0) < 1e-9 and args.cpu_sample_mbp > 0))
         if want_other:
             eng.close(); eng = None                              # (the sub-processes get the GPU and the host memory to themselves)
             other = {}
@@ -695,7 +707,7 @@ def main():
                     # against the oracle on all cores too — planes only: its text would be 72 GB
                     "config5_full_one_gpu": ["--mode", "strong", "--contig-mbp", "50", "--full-check", "2", "--steps", "10", "--warmup", "2"]}
             for key, extra in subs.items():
-                cmd = [sys.executable, os.path.abspath(__file__), "--steps", "60", "--warmup", "5", "--cpu-ref-mbp", "0", "--e2e-mbp", "0", "--abi-mbp", "0", "--other-configs", "0"] + extra
+                cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "60", "--warmup", "5", "--cpu-ref-mbp", "0", "--e2e-mbp", "0", "--abi-mbp", "0", "--other-configs", "0"] + extra
                 try:
                     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
                     sub = json.loads([l for l in out.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -709,7 +721,7 @@ def main():
         # lookups (tools/e2e_configs.py validates against oracle/_ref/bam-readcount-ref, the reference's own main())
         e2e_sites = e2e_tumor = None; e2e_sharded = None
         dist_backend = dist.get_backend() if dist is not None else None
-        want_e2e = (args.e2e_configs == 1 or (args.e2e_configs < 0 and (want_other or (world > 1 and args.mode == "weak" and config == "wgs30x")))) and os.path.exists(CLI) and not args.force_dist
+        want_e2e = extras and (args.e2e_configs == 1 or (args.e2e_configs < 0 and (want_other or (world > 1 and args.mode == "weak" and config == "wgs30x")))) and os.path.exists(CLI) and not args.force_dist
         if want_e2e and world > 1:
             # an N-rank run: the other ranks are done (their engines close, their processes end) — the drop-in's own one-rank-per-GPU
             # launcher gets the node's GPUs to itself; nothing below is a collective
@@ -754,7 +766,7 @@ def main():
         line = {
             "metric": "pileup base-events/sec", "value": round(value, 1), "unit": "events/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak" if args.mode == "weak" else "strong", "vs_baseline": None, "dtype": "u32+f32", "data": "synthetic" + (" (TEST RUN: every rank on GPU 0, process group on gloo — BRC_BENCH_SHARE_GPU0)" if share_gpu0 else ""),
+            "scaling": "weak" if args.mode == "weak" else "strong", "full": extras, "vs_baseline": None, "dtype": "u32+f32", "data": "synthetic" + (" (TEST RUN: every rank on GPU 0, process group on gloo — BRC_BENCH_SHARE_GPU0)" if share_gpu0 else ""),
             "config": {"workload": what, "mode": args.mode, "reads_per_gpu": int(len(region_reads["pos"])), "piece_steps": piece_steps,
                        "events_per_step": int(ev_total), "positions_per_step": int(pos_total), "parallelism": "interval-shard x%d" % world},
             "positions_per_s": round(pos_total * args.steps / tmax, 1),

@@ -78,6 +78,27 @@ def test_two_ranks_reduce_what_each_rank_owns(mode):
         assert own[0]["own_events"] != own[1]["own_events"]                  # different contigs (seed per rank)
 
 
+@pytest.mark.parametrize("mode", sorted(MODES))
+def test_every_rank_validates_its_own_share_with_full_only(mode):
+    """A plain run checks nothing; with --full every rank holds a prefix of its own interval (its own sites) against the oracle
+    and the verdicts are MIN-reduced onto the line."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "sim")])
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    lines = {}
+    for full in ([], ["--full"]):
+        s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
+        run = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
+                              os.path.join(ROOT, "bench.py"), "--gpus", "2"] + full + MODES[mode] + COMMON, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
+        assert run.returncode == 0, run.stderr.decode()[-2000:]
+        lines[bool(full)] = line_of(run.stdout)
+    assert lines[False]["validated"] is None and all("validated_ok" not in x for x in lines[False]["per_rank"])
+    v = lines[True]["validated"]
+    assert v["all_ranks_ok"] is True and v["own_error"] is None and v["own"]
+    assert all(x["validated_ok"] is True and x["validated_events"] > 0 for x in lines[True]["per_rank"])
+    for k in ("events_per_step", "positions_per_step", "own_events", "own_positions"):
+        assert lines[False][k] == lines[True][k] > 0
+
+
 @pytest.mark.parametrize("mode", ["weak", "strong"])
 def test_dump_outputs_are_reproducible_and_equal_the_oracle(mode, tmp_path, oracle_lib):
     """--dump-outputs: float32 / float64 arrays, at most 64 MB, the same on every run with the same inputs whatever --steps is,

@@ -19,7 +19,8 @@ def free_port():
     return p
 
 
-SMALL = ["--steps", "3", "--warmup", "1", "--cpu-sample-mbp", "0", "--e2e-mbp", "0", "--abi-mbp", "0", "--other-configs", "0", "--e2e-configs", "0"]
+# (--full: every rank's validation of its own interval and the e2e_sharded legs are not part of a plain run)
+SMALL = ["--full", "--steps", "3", "--warmup", "1", "--cpu-sample-mbp", "0", "--e2e-mbp", "0", "--abi-mbp", "0", "--other-configs", "0", "--e2e-configs", "0"]
 
 
 @pytest.mark.gpu
@@ -94,7 +95,7 @@ def test_bench_two_ranks_on_one_gpu_run_the_whole_n_rank_flow():
     round 6 — rank 0's e2e_sharded legs: configs 4 and 5 through `bam-readcount --brc-ranks 2`, whole output byte-identical to one process."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BRC_BENCH_SHARE_GPU0="1")
     run = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--mode", "weak", "--contig-mbp", "2", "--steps", "3", "--warmup", "1", "--cpu-sample-mbp", "0", "--e2e-mbp", "0",
+                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--mode", "weak", "--contig-mbp", "2", "--steps", "3", "--warmup", "1", "--cpu-sample-mbp", "0", "--e2e-mbp", "0",
                           "--abi-mbp", "0", "--other-configs", "0", "--e2e-configs", "1", "--e2e-sites-mbp", "1", "--e2e-tumor-mbp", "0.4"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=1500)
     assert run.returncode == 0, run.stderr.decode()[-3000:]

@@ -1,4 +1,4 @@
-"""tools/fullcheck.py (the whole-region validation bench.py runs on the GPU box) on the CPU: the device side played by the lane
+"""tools/fullcheck.py (the whole-region validation `bench.py --full` runs on the GPU) on the CPU: the device side played by the lane
 simulator, two oracle processes.  The check must pass on equal results and must name the window and the part that differs
 otherwise."""
 import os

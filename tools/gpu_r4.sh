@@ -5,10 +5,10 @@ for what in "$@"; do
   case $what in
     suite) ( time timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -25 ) > $out/pytest_gpu_$tag.log 2>&1 ;;
     suitex) ( time timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -40 ) > $out/pytest_gpu_$tag.log 2>&1 ;;
-    bench) ( time timeout 1500 python bench.py --steps 20 --warmup 5 ) > $out/bench_$tag.log 2> $out/bench_$tag.err ;;
-    bench300) ( time timeout 1500 python bench.py ) > $out/bench300_$tag.log 2> $out/bench300_$tag.err ;;
+    bench) ( time timeout 1500 python bench.py --full --steps 20 --warmup 5 ) > $out/bench_$tag.log 2> $out/bench_$tag.err ;;
+    bench300) ( time timeout 1500 python bench.py --full ) > $out/bench300_$tag.log 2> $out/bench300_$tag.err ;;
     ab) ( time timeout 1200 python tools/gpu_ab_multi.py --libs $AB_LIBS --reps ${AB_REPS:-3} --shapes ${AB_SHAPES:-tumor,wgs} ) > $out/ab_$tag.log 2>&1 ;;
-    sites) ( time timeout 900 python bench.py --mode sites --steps 60 --warmup 5 --e2e-mbp 0 --other-configs 0 ) > $out/sites_$tag.log 2> $out/sites_$tag.err ;;
+    sites) ( time timeout 900 python bench.py --full --mode sites --steps 60 --warmup 5 --e2e-mbp 0 --other-configs 0 ) > $out/sites_$tag.log 2> $out/sites_$tag.err ;;
     e2e) ( python - <<'PY'
 import os, sys, time, subprocess, tempfile
 sys.path.insert(0, "tools"); sys.path.insert(0, ".")
@@ -27,7 +27,7 @@ for rep in range(3):
     print("rep", rep, round(time.perf_counter() - t0, 3), "s"); print(p.stderr.decode()[-1500:])
 PY
       ) > $out/e2e_$tag.log 2>&1 ;;
-    quick) ( time timeout 900 python bench.py --steps 20 --warmup 5 --other-configs 0 --e2e-mbp 0 ) > $out/quick_$tag.log 2> $out/quick_$tag.err ;;
+    quick) ( time timeout 900 python bench.py --full --steps 20 --warmup 5 --other-configs 0 --e2e-mbp 0 ) > $out/quick_$tag.log 2> $out/quick_$tag.err ;;
   esac
 done
 tail -c 1500 $out/*_$tag.log

@@ -8,7 +8,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
     for lib in ${LIBS:-default}; do
       A="--mode weak --config $cfg"; [ $cfg = tumor200x ] && A="--mode strong --contig-mbp 6.25"
       name=$(basename $lib .so)
-      ( [ $lib != default ] && export BRC_HIP_LIB=$PWD/$lib; timeout 600 python bench.py --gpus 1 --steps 30 --warmup 5 --cpu-sample-mbp ${SAMPLE:-1} --cpu-ref-mbp 0 --e2e-mbp 0 --abi-mbp 0 --other-configs 0 --e2e-configs 0 --full-check 0 $A ) > $out/${cfg}_${name}_$r.log 2>&1
+      ( [ $lib != default ] && export BRC_HIP_LIB=$PWD/$lib; timeout 600 python bench.py --full --gpus 1 --steps 30 --warmup 5 --cpu-sample-mbp ${SAMPLE:-1} --cpu-ref-mbp 0 --e2e-mbp 0 --abi-mbp 0 --other-configs 0 --e2e-configs 0 --full-check 0 $A ) > $out/${cfg}_${name}_$r.log 2>&1
       grep '^{' $out/${cfg}_${name}_$r.log | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print('$cfg', '$name', $r, d['ms_per_step'], d['roofline']['kernel_ms'], d['per_rank'][0].get('hbm_bytes'))" || tail -3 $out/${cfg}_${name}_$r.log
     done
   done
