@@ -563,3 +563,96 @@ class Inflater:
         k = C.c_double(); c = C.c_double(); bi = C.c_uint64(); bo = C.c_uint64()
         self.lib.brc_inflater_last_timing(self.h, C.byref(k), C.byref(c), C.byref(bi), C.byref(bo))
         return dict(kernel_s=k.value, call_s=c.value, bytes_in=bi.value, bytes_out=bo.value)
+
+
+# ---------------------------------------------------------------- the BGZF deflater (include/brc_deflate.h)
+DEFLATE_LIB = os.path.join(HERE, "csrc", "libbrc_deflate_hip.so")
+DEFLATE_EXPORTS = [
+    "brc_deflater_create", "brc_deflater_destroy", "brc_deflater_kind", "brc_deflater_last_error", "brc_deflate_bound",
+    "brc_deflate_bgzf", "brc_deflate_eof_block", "brc_deflate_host_alloc", "brc_deflate_host_free", "brc_deflater_last_timing",
+]
+DEFLATE_MEMBER_INPUT = 0xff00
+
+
+def _bind_deflate(L):
+    L.brc_deflater_kind.restype = C.c_char_p
+    L.brc_deflater_last_error.restype = C.c_char_p; L.brc_deflater_last_error.argtypes = [C.c_void_p]
+    L.brc_deflater_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    L.brc_deflater_destroy.argtypes = [C.c_void_p]; L.brc_deflater_destroy.restype = None
+    L.brc_deflate_bound.restype = C.c_size_t; L.brc_deflate_bound.argtypes = [C.c_size_t]
+    L.brc_deflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.brc_deflate_eof_block.restype = C.c_void_p; L.brc_deflate_eof_block.argtypes = [C.POINTER(C.c_size_t)]
+    L.brc_deflate_host_alloc.restype = C.c_void_p; L.brc_deflate_host_alloc.argtypes = [C.c_size_t]
+    L.brc_deflate_host_free.restype = None; L.brc_deflate_host_free.argtypes = [C.c_void_p]
+    L.brc_deflater_last_timing.restype = None
+    L.brc_deflater_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    return L
+
+
+class Deflater:
+    """One deflater handle of a library exporting include/brc_deflate.h: the product's libbrc_deflate_hip.so (default; raises when it
+    is not built or there is no device — nothing falls back) or the CPU build of the same compressor (tests/sim_deflate)."""
+
+    def __init__(self, path=None, device=0):
+        path = path or DEFLATE_LIB
+        if not os.path.exists(path):
+            raise BrcError("deflater library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
+        self.path = path
+        self.lib = L = _bind_deflate(C.CDLL(path))
+        h = C.c_void_p()
+        rc = L.brc_deflater_create(device, C.byref(h))
+        if rc != 0:
+            e = BrcError("brc_deflater_create failed: %d" % rc)
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def kind(self):
+        return self.lib.brc_deflater_kind().decode()
+
+    def close(self):
+        if self.h:
+            self.lib.brc_deflater_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def bound(self, n):
+        return int(self.lib.brc_deflate_bound(n))
+
+    def eof_block(self):
+        n = C.c_size_t()
+        p = self.lib.brc_deflate_eof_block(C.byref(n))
+        return C.string_at(p, n.value)
+
+    def deflate_raw(self, src, dst_cap=None, handle=True):
+        """brc_deflate_bgzf as it is: (rc, bytes of dst, members).  dst_cap None: the bound.  dst is pre-filled with 0xA5 (what a
+        refused call must leave untouched).  handle False: a NULL handle."""
+        if isinstance(src, np.ndarray):
+            sbuf = src if src.size else np.zeros(1, np.uint8); n_src = int(src.size)
+        else:
+            src = bytes(src); n_src = len(src)
+            sbuf = np.frombuffer(src, np.uint8) if src else np.zeros(1, np.uint8)
+        cap = self.bound(n_src) if dst_cap is None else dst_cap
+        dst = np.full(max(cap, 1), 0xA5, np.uint8)
+        got = C.c_size_t(0); nm = C.c_size_t(0)
+        rc = self.lib.brc_deflate_bgzf(self.h if handle else None, sbuf.ctypes.data, n_src, dst.ctypes.data, cap, C.byref(got), C.byref(nm))
+        if rc != 0:
+            return rc, dst[:cap].tobytes(), 0
+        return rc, dst[:got.value].tobytes(), nm.value
+
+    def deflate(self, src):
+        """Any bytes -> whole BGZF members back to back (no end-of-file member)."""
+        rc, out, _ = self.deflate_raw(src)
+        if rc != 0:
+            raise BrcError("brc_deflate_bgzf: %d (%s)" % (rc, self.lib.brc_deflater_last_error(self.h).decode()))
+        return out
+
+    def last_timing(self):
+        k = C.c_double(); c = C.c_double(); bi = C.c_uint64(); bo = C.c_uint64()
+        self.lib.brc_deflater_last_timing(self.h, C.byref(k), C.byref(c), C.byref(bi), C.byref(bo))
+        return dict(kernel_s=k.value, call_s=c.value, bytes_in=bi.value, bytes_out=bo.value)

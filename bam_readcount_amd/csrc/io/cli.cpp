@@ -25,6 +25,16 @@
 // this executable; a missing library or device is an error, exit code 1) — instead of one block at a time on the fetch threads.
 // Output, messages and exit codes are those of the switch off.  Every rank opens its own inflater on its own GPU; CRAM input has no
 // BGZF blocks and says once that the switch is ignored.
+//
+// --brc-bgzf-output (BRC_BGZF_OUTPUT=1; off by default): everything this program would write to stdout leaves as BGZF members instead,
+// compressed on the GPU by the deflater library of include/brc_deflate.h — found with dlopen (BRC_DEFLATE_LIB, else
+// libbrc_deflate_hip.so next to this executable; a missing library or device is an error, exit code 1, nothing on stdout).  One sink
+// (BgzfSink below) sits behind every place that writes text; it gathers the text in page-locked buffers and compresses a batch per call
+// on a thread of its own.  The end-of-file member follows the last member exactly once (with --brc-ranks: the coordinator appends it
+// behind the last rank's members).  stderr and the exit code are those of the switch off; zcat of stdout is the switch-off stdout.
+// --help and --version print their plain text whatever the switch says: they end the run before any input is opened or any library
+// loaded, and what they print is for a person, not a file of records.  A write error on stdout other than a closed pipe ends the run
+// with a message and exit code 1.
 #include <errno.h>
 #include <limits.h>
 #include <stdio.h>
@@ -58,6 +68,7 @@ struct Options {
     long long streams = 0;          // engines per GPU (0: one; every engine already overlaps decode | GPU | format of consecutive pieces): --brc-streams
     long long ranks = 0;            // processes, one per GPU: --brc-ranks (BRC_RANKS)
     std::string rank_of;            // "r:N": this process IS rank r of N (what the coordinating process starts its children with): --brc-rank-of
+    bool bgzf_output = false;       // stdout as BGZF members compressed by the deflater library (include/brc_deflate.h): --brc-bgzf-output (BRC_BGZF_OUTPUT=1)
     bool device_inflate = false;    // BGZF blocks inflated by the inflater library (include/brc_inflate.h): --brc-device-inflate (BRC_DEVICE_INFLATE=1)
     std::string tmpdir;             // where the ranks behind the first keep their text until its turn comes: --brc-tmpdir (TMPDIR, /tmp)
 };
@@ -93,6 +104,7 @@ static const OptSpec kSpecs[] = {
     {'d', "max-count", true}, {'l', "site-list", true}, {'f', "reference-fasta", true}, {'D', "print-individual-mapq", true},
     {'p', "per-library", false}, {'w', "max-warnings", true}, {'i', "insertion-centric", false}, {0, "brc-chunk", true}, {1, "brc-plan", true}, {2, "brc-gpus", true}, {3, "brc-streams", true},
     {4, "brc-ranks", true}, {5, "brc-rank-of", true}, {6, "brc-tmpdir", true}, {7, "brc-device-inflate", false},
+    {8, "brc-bgzf-output", false},
 };
 
 static bool apply(Options& o, const OptSpec& sp, const std::string& v, std::string* err) {
@@ -125,6 +137,7 @@ static bool apply(Options& o, const OptSpec& sp, const std::string& v, std::stri
         case 5: o.rank_of = v; return true;
         case 6: o.tmpdir = v; return true;
         case 7: o.device_inflate = true; return true;
+        case 8: o.bgzf_output = true; return true;
         default: if (!to_ll(&x)) return false; o.chunk_bp = x; o.chunk_given = true; return true;
     }
 }
@@ -299,10 +312,82 @@ static void print_warn_events(const char* ev, size_t n, long long max, int64_t* 
     }
 }
 
+// --brc-bgzf-output: the one place stdout's bytes go when the switch is on.  Text is gathered in two page-locked buffers of one batch
+// each; a full buffer is handed to the sink's own thread, which compresses it in one call of the deflater library (a batch is cut into
+// members of 0xff00 input bytes from its start, so only a batch's last member is short) and writes the members, in order, while the
+// caller fills the other buffer.  One caller at a time (the formatter thread of a region, else the main thread).
+#include <condition_variable>
+static const unsigned char kBgzfEof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+struct BgzfSink {
+    void* handle = nullptr;
+    int (*deflate)(void*, const void*, size_t, void*, size_t, size_t*, size_t*) = nullptr;
+    const char* (*last_error)(const void*) = nullptr;
+    size_t batch = (size_t)32 << 20;
+    char* buf[2] = {nullptr, nullptr}; size_t fill[2] = {0, 0}; char* dst = nullptr; size_t dst_cap = 0;
+    int cur = 0, pending = -1;              // the buffer being filled; the buffer the thread is compressing (-1: none)
+    bool stop = false, failed = false, finished = false; std::string err;
+    std::mutex mu; std::condition_variable cv; std::thread worker;
+    uint64_t calls = 0, bytes_in = 0, bytes_out = 0; double seconds = 0;
+    // a closed pipe: like the reference, carry on silently; any other error (a full disk) is the run's: message and exit code 1
+    bool write_fd(const char* p, size_t n) {
+        while (n) {
+            const ssize_t w = ::write(1, p, n);
+            if (w < 0) {
+                if (errno == EINTR) continue;
+                if (errno == EAGAIN) { usleep(1000); continue; }
+                if (errno != EPIPE && !failed) { failed = true; err = std::string("cannot write to stdout: ") + strerror(errno); }
+                return false;
+            }
+            p += w; n -= (size_t)w;
+        }
+        return true;
+    }
+    void run() {
+        std::unique_lock<std::mutex> lk(mu);
+        for (;;) {
+            cv.wait(lk, [&]() { return pending >= 0 || stop; });
+            if (pending < 0) return;
+            const int b = pending;
+            lk.unlock();
+            const auto t0 = std::chrono::steady_clock::now();
+            size_t got = 0, nm = 0;
+            const int rc = failed ? 0 : deflate(handle, buf[b], fill[b], dst, dst_cap, &got, &nm);
+            if (rc != 0) { failed = true; err = last_error ? last_error(handle) : ""; }
+            else if (!failed) { write_fd(dst, got); ++calls; bytes_in += fill[b]; bytes_out += got; }
+            seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            lk.lock();
+            fill[b] = 0; pending = -1; cv.notify_all();
+        }
+    }
+    void hand_over() {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&]() { return pending < 0; });
+        pending = cur; cur ^= 1; cv.notify_all();
+    }
+    void write(const char* t, size_t n) {
+        while (n) {
+            const size_t k = std::min(n, batch - fill[cur]);
+            memcpy(buf[cur] + fill[cur], t, k); fill[cur] += k; t += k; n -= k;
+            if (fill[cur] == batch) hand_over();
+        }
+    }
+    // the rest of the text, then (eof) the end-of-file member: once, whatever calls it again
+    void finish(bool eof) {
+        if (finished) return;
+        finished = true;
+        if (fill[cur]) hand_over();
+        { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return pending < 0; }); stop = true; cv.notify_all(); }
+        if (worker.joinable()) worker.join();
+        if (eof && !failed) write_fd((const char*)kBgzfEof, sizeof kBgzfEof);
+    }
+};
+static BgzfSink* g_sink = nullptr;           // set before the first byte of text, never cleared
+
 // Many pieces of text -> stdout with few system calls: a region's text arrives as thousands of pieces (the device's text
 // between the lines the host rewrote); one write() each would cost more than producing them.
 #include <sys/uio.h>
 static void write_parts(const char* const* parts, const size_t* lens, size_t n) {
+    if (g_sink) { for (size_t i = 0; i < n; ++i) if (lens[i]) g_sink->write(parts[i], lens[i]); return; }
     fflush(stdout);
     const int fd = fileno(stdout);
     std::vector<struct iovec> iov; iov.reserve(1024);
@@ -356,7 +441,7 @@ struct Ctx {
         }
         print_warn_events(ev, n, opt.max_warnings, wcount, stderr);
     }
-    void emit(const char* t, size_t n) { if (!n) return; if (out_buf) out_buf->append(t, n); else fwrite(t, 1, n, stdout); }
+    void emit(const char* t, size_t n) { if (!n) return; if (out_buf) out_buf->append(t, n); else if (g_sink) g_sink->write(t, n); else fwrite(t, 1, n, stdout); }
     // several engines, region pieces: the text stays in the engine's buffer (no copy of hundreds of megabytes per piece);
     // the main thread writes it from there, and this engine's next format call waits for that (pre_format)
     std::function<bool()> need_engine;      // the first context's engine is created in the background: wait for it (false: it failed)
@@ -919,6 +1004,43 @@ static int open_inflater(Ctx& c, int device) {
     return 0;
 }
 
+// --brc-bgzf-output: the deflater library through dlopen, and the sink that feeds it.  A missing library, entry point or device ends the
+// run with nothing on stdout — there is no quiet return to plain text.
+static int open_bgzf_sink(int device) {
+    std::string path;
+    if (const char* e = getenv("BRC_DEFLATE_LIB")) path = e;
+    else {
+        char exe[PATH_MAX]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
+        path = n > 0 ? std::string(exe, (size_t)n) : std::string("bam-readcount");
+        const size_t sl = path.rfind('/');
+        path = (sl == std::string::npos ? std::string(".") : path.substr(0, sl)) + "/libbrc_deflate_hip.so";
+    }
+    void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!lib) { fprintf(stderr, "bam-readcount: --brc-bgzf-output: cannot load the deflater library %s: %s\n", path.c_str(), dlerror()); return 1; }
+    typedef int (*create_fn)(int, void**);
+    create_fn create = (create_fn)dlsym(lib, "brc_deflater_create");
+    void* fn = dlsym(lib, "brc_deflate_bgzf");
+    size_t (*bound)(size_t) = (size_t (*)(size_t))dlsym(lib, "brc_deflate_bound");
+    void* (*halloc)(size_t) = (void* (*)(size_t))dlsym(lib, "brc_deflate_host_alloc");
+    if (!create || !fn || !bound || !halloc) { fprintf(stderr, "bam-readcount: --brc-bgzf-output: cannot load the deflater library %s: it does not export the deflater of include/brc_deflate.h\n", path.c_str()); return 1; }
+    void* h = nullptr;
+    const int rc = create(device, &h);
+    if (rc != 0 || !h) { fprintf(stderr, "bam-readcount: --brc-bgzf-output: cannot load the deflater library %s: no deflater on device %d: %s\n", path.c_str(), device, brc_strerror(rc)); return 1; }
+    BgzfSink* s = new BgzfSink();
+    s->handle = h;
+    s->deflate = (int (*)(void*, const void*, size_t, void*, size_t, size_t*, size_t*))fn;
+    s->last_error = (const char* (*)(const void*))dlsym(lib, "brc_deflater_last_error");
+    // the batch: DESIGN.md 6b (BRC_BGZF_BATCH: bytes; tests cut their kilobytes of text into several calls)
+    // (within 64 KB .. 1 GB: the library holds about three times the batch on the device, and three page-locked buffers of it here)
+    if (const char* b = getenv("BRC_BGZF_BATCH")) { const long long v = atoll(b); if (v > 0) s->batch = (size_t)std::min<long long>(std::max<long long>(v, 65536), 1ll << 30); }
+    s->dst_cap = bound(s->batch);
+    s->buf[0] = (char*)halloc(s->batch); s->buf[1] = (char*)halloc(s->batch); s->dst = (char*)halloc(s->dst_cap);
+    if (!s->buf[0] || !s->buf[1] || !s->dst) { fprintf(stderr, "bam-readcount: --brc-bgzf-output: no page-locked memory for batches of %zu bytes\n", s->batch); return 1; }
+    s->worker = std::thread([s]() { s->run(); });
+    g_sink = s;
+    return 0;
+}
+
 // A crash must not be silent: frames of the faulting thread (module + offset: `addr2line -e <module> <offset>` resolves
 // them) go to stderr before the default action takes the process down.
 #include <execinfo.h>
@@ -1043,6 +1165,7 @@ static int coordinate(int argc, char** argv, const Options& o, int N) {
         return c.reaped;
     };
     int ret = 0;
+    bool text_out = false;                          // some rank has (or may have) written text: rank 0 ended well, or a later rank's bytes were copied
     int64_t gcount[BRC_N_WARN] = {0, 0, 0, 0};
     std::vector<double> secs((size_t)N, 0.0); std::vector<double> done_at((size_t)N, 0.0);
     std::vector<char> buf((size_t)1 << 20);
@@ -1086,7 +1209,7 @@ static int coordinate(int argc, char** argv, const Options& o, int N) {
                         if (!write_all(1, buf.data(), (size_t)g)) { off = fs.st_size; break; }     // (a closed pipe: like the reference, carry on silently)
                         off += g;
                     }
-                    moved = true;
+                    moved = true; text_out = true;
                 }
                 if (finished) { struct stat f2; if (fstat(c.out, &f2) == 0 && f2.st_size > off) continue; break; }
                 if (!moved) poll_status(r, 1);
@@ -1098,8 +1221,8 @@ static int coordinate(int argc, char** argv, const Options& o, int N) {
         int rc = 0;
         {
             const std::string& sline = status_line[(size_t)r];
-            long long w[BRC_N_WARN] = {0, 0, 0, 0}; int src = 1; double s = 0;
-            if (sscanf(sline.c_str(), "%d %lld %lld %lld %lld %lf", &src, &w[0], &w[1], &w[2], &w[3], &s) == 6) { secs[(size_t)r] = s; if (r == 0) for (int k = 0; k < BRC_N_WARN; ++k) gcount[k] = w[k]; rc = src; }
+            long long w[BRC_N_WARN] = {0, 0, 0, 0}; int src = 1, wrote = 0; double s = 0;
+            if (sscanf(sline.c_str(), "%d %lld %lld %lld %lld %lf %d", &src, &w[0], &w[1], &w[2], &w[3], &s, &wrote) >= 6) { if (wrote) text_out = true; secs[(size_t)r] = s; if (r == 0) for (int k = 0; k < BRC_N_WARN; ++k) gcount[k] = w[k]; rc = src; }
             else { reap(c, true); rc = WIFEXITED(c.wstatus) && WEXITSTATUS(c.wstatus) ? WEXITSTATUS(c.wstatus) : 1; }           // (a rank that ended without a word did not end well: wait for it, say how it went)
         }
         if (r > 0) {
@@ -1115,6 +1238,7 @@ static int coordinate(int argc, char** argv, const Options& o, int N) {
             }
         }
         if (rc) ret = rc == 127 ? 1 : rc;
+        else if (r == 0) text_out = true;
         if (c.reaped && WIFSIGNALED(c.wstatus)) { ret = 1; fprintf(stderr, "bam-readcount: rank %d ended on signal %d\n", r, WTERMSIG(c.wstatus)); }
     }
     // a failed run: the ranks behind the failure are stopped, their text is dropped.  (Ranks that are done are not waited for: see above.)
@@ -1126,6 +1250,9 @@ static int coordinate(int argc, char** argv, const Options& o, int N) {
         fprintf(stderr, "; all told %.3f s\n", now_s() - t0);
     }
     fflush(stdout); fflush(stderr);
+    // --brc-bgzf-output: the ranks wrote members and no end-of-file member; it follows the last rank's bytes, once
+    // (a run whose first rank failed before any text — no deflater to be had — leaves stdout empty)
+    if (!to_null && (ret == 0 || text_out) && (o.bgzf_output || (getenv("BRC_BGZF_OUTPUT") && atoi(getenv("BRC_BGZF_OUTPUT")) != 0))) write_all(1, (const char*)kBgzfEof, sizeof kBgzfEof);
     return ret;
 }
 
@@ -1178,7 +1305,7 @@ int main(int argc, char** argv) {
     const double t_start = now_s();
     auto leave = [&](int rc) {                      // a rank tells the coordinator how it ended (exit code, ReadWarnings' counters, seconds)
         if (my_rank >= 0 && status_fd >= 0) {
-            char b[256]; const int n = snprintf(b, sizeof b, "%d %lld %lld %lld %lld %.6f\n", rc, (long long)c.wcount[0], (long long)c.wcount[1], (long long)c.wcount[2], (long long)c.wcount[3], now_s() - t_start);
+            char b[256]; const int n = snprintf(b, sizeof b, "%d %lld %lld %lld %lld %.6f %d\n", rc, (long long)c.wcount[0], (long long)c.wcount[1], (long long)c.wcount[2], (long long)c.wcount[3], now_s() - t_start, g_sink && g_sink->calls ? 1 : 0);   // (last: --brc-bgzf-output, this rank wrote members)
             fflush(stdout); fflush(stderr);
             write_all(status_fd, b, (size_t)n);
         }
@@ -1226,6 +1353,13 @@ int main(int argc, char** argv) {
     std::thread inf_thread; int inf_rc = 0;
     if (c.opt.device_inflate) inf_thread = std::thread([&]() { inf_rc = open_inflater(c, devices[0]); });
     struct JoinInf { std::thread& t; ~JoinInf() { if (t.joinable()) t.join(); } } join_inf{inf_thread};
+    // --brc-bgzf-output: the same for the deflater behind stdout.  Whoever leaves before any text was written (bail) still leaves a whole
+    // BGZF file — its end-of-file member — unless the deflater itself could not be had: then stdout stays empty.
+    if (!o.bgzf_output && getenv("BRC_BGZF_OUTPUT") && atoi(getenv("BRC_BGZF_OUTPUT")) != 0) c.opt.bgzf_output = true;
+    std::thread def_thread; int def_rc = 0;
+    if (c.opt.bgzf_output) def_thread = std::thread([&]() { def_rc = open_bgzf_sink(devices[0]); });
+    struct JoinDef { std::thread& t; ~JoinDef() { if (t.joinable()) t.join(); } } join_def{def_thread};
+    auto bail = [&](int rc) { if (def_thread.joinable()) def_thread.join(); if (g_sink) g_sink->finish(my_rank < 0); return leave(rc); };
     // The engine (HIP runtime start, streams) is created on a thread of its own while this one reads the index and the site
     // list and — inside the first work item — the reference and the first reads; whoever needs the engine waits for it.
     double t_engine0 = 0;
@@ -1269,8 +1403,8 @@ int main(int argc, char** argv) {
     };
     if (!o.site_list.empty()) {
         FILE* fp = fopen(o.site_list.c_str(), "r");
-        if (!fp) { if (lead) fprintf(stderr, "Failed to open region list file: %s\n", o.site_list.c_str()); return leave(1); }            // :535-538
-        if (!c.is_cram && !c.idx.load(o.bam)) { if (lead) fprintf(stderr, "BAM indexing file is not available.\n"); return leave(1); }                  // :548-551
+        if (!fp) { if (lead) fprintf(stderr, "Failed to open region list file: %s\n", o.site_list.c_str()); return bail(1); }            // :535-538
+        if (!c.is_cram && !c.idx.load(o.bam)) { if (lead) fprintf(stderr, "BAM indexing file is not available.\n"); return bail(1); }                  // :548-551
         // the planner needs -d to be out of play (its drop rule depends on what else is buffered) and narrow lines
         const bool plan = o.plan_sites > 0 && o.max_cnt >= 1000000 && !c.is_cram;
         Work pend; pend.kind = 1; int64_t pend_bp = 0;
@@ -1305,7 +1439,7 @@ int main(int argc, char** argv) {
         free(line);
         fclose(fp);
     } else if (!o.regions.empty()) {
-        if (!c.is_cram && !c.idx.load(o.bam)) { if (lead) fprintf(stderr, "BAM indexing file is not available.\n"); return leave(1); }                  // :637-640
+        if (!c.is_cram && !c.idx.load(o.bam)) { if (lead) fprintf(stderr, "BAM indexing file is not available.\n"); return bail(1); }                  // :637-640
         for (const std::string& r : o.regions) {
             int tid; int64_t beg, end; std::string log;
             if (!parse_region(c.header(), r, &tid, &beg, &end, &log)) {              // :645-648: the regions before it have been printed
@@ -1317,7 +1451,7 @@ int main(int argc, char** argv) {
     } else {
         if (lead) fprintf(stderr, "bam-readcount: give a region or a site list (-l); the reference's whole-file mode skips its per-read "
                                   "pre-processing (bamreadcount.cpp:624 FIXME) and is not reproduced\n");
-        return leave(1);
+        return bail(1);
     }
 
     if (atoms) {
@@ -1361,7 +1495,8 @@ int main(int argc, char** argv) {
         }
     }
 
-    if (inf_thread.joinable()) { inf_thread.join(); if (inf_rc != 0) return leave(1); }      // no reader starts before the inflater exists (or the run ends: no return to the host path)
+    if (def_thread.joinable()) { def_thread.join(); if (def_rc != 0) return leave(1); }      // no text is written before the sink exists (or the run ends: no return to plain text)
+    if (inf_thread.joinable()) { inf_thread.join(); if (inf_rc != 0) return bail(1); }      // no reader starts before the inflater exists (or the run ends: no return to the host path)
     if (items.size() < N) N = std::max<size_t>(items.size(), 1);      // engines without work are never created
     if (N > 1) {    // the engines share this process's CPUs: each gets its part of the decode and formatter pools
         g_engines = (unsigned)N;
@@ -1489,7 +1624,7 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < items.size(); ++i) {
             Work& w = items[i];
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return w.done; }); }
-            if (!w.out.empty()) fwrite(w.out.data(), 1, w.out.size(), stdout);
+            if (!w.out.empty()) { if (g_sink) g_sink->write(w.out.data(), w.out.size()); else fwrite(w.out.data(), 1, w.out.size(), stdout); }
             if (w.n_parts) write_parts(w.parts, w.lens, w.n_parts);
             if (!w.wev.empty()) print_warn_events(w.wev.data(), w.wev.size(), c.opt.max_warnings, gcount, stderr);   // the global -w counters, in file order
             if (!w.err.empty()) fputs(w.err.c_str(), stderr);
@@ -1504,6 +1639,11 @@ int main(int argc, char** argv) {
         if (!clean_exit) for (auto& p : ctxs) (void)p.release();
     }
     const std::string who = my_rank >= 0 ? "rank " + std::to_string(my_rank) + ": " : std::string();
+    if (g_sink) {       // the last batch; the end-of-file member unless this is a rank (the coordinator writes it behind the last rank)
+        g_sink->finish(my_rank < 0);
+        if (g_sink->failed) { fprintf(stderr, "bam-readcount: --brc-bgzf-output: the deflater failed: %s\n", g_sink->err.c_str()); ret = 1; }
+        if (getenv("BRC_CLI_TIMING")) fprintf(stderr, "%sdevice deflate: %llu calls, %.1f MB in, %.1f MB out, %.3f s\n", who.c_str(), (unsigned long long)g_sink->calls, g_sink->bytes_in / 1e6, g_sink->bytes_out / 1e6, g_sink->seconds);
+    }
     if (getenv("BRC_CLI_TIMING")) fprintf(stderr, "%sstartup: open inputs %.3f s, create engine %.3f s\n", who.c_str(), t_inputs - t_start, t_engine0 - t_inputs);
     if (getenv("BRC_CLI_TIMING")) fprintf(stderr, "%stiming: fetch+decode %.3f s, engine (push, upload, kernels, download) %.3f s, format %.3f s, write %.3f s\n", who.c_str(), c.t_fetch, c.t_engine, c.t_format, c.t_write);
     if (getenv("BRC_CLI_TIMING") && c.inf)
