@@ -20,7 +20,7 @@ F_NAMES = ["sev", "sq2", "snm", "s3p"]
 EXPORTS = [
     "brc_strerror", "brc_last_error", "brc_kernel_name", "brc_engine_kind", "brc_create", "brc_destroy",
     "brc_begin_region", "brc_push_reads", "brc_upload", "brc_compute", "brc_fetch_result", "brc_end_region",
-    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows", "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts", "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned", "brc_region_piece_steps",
+    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows", "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts", "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned", "brc_region_piece_steps", "brc_device_view_get",
 ]
 
 
@@ -56,6 +56,16 @@ class Result(C.Structure):
                 ("warn", C.c_uint64 * NWARN)]
 
 
+class DeviceView(C.Structure):
+    """brc_device_view (include/brc.h): the compact results of a computed region where they lie."""
+    _fields_ = [("memory", C.c_int32), ("device", C.c_int32), ("n_lib", C.c_int32), ("pos0", C.c_int32), ("n_pos", C.c_int64),
+                ("stride", C.c_int64), ("ncol", C.c_void_p), ("depth", C.c_void_p), ("slotid", C.c_void_p), ("si", C.c_void_p),
+                ("unavail", C.c_void_p), ("sf", C.c_void_p), ("xagg", C.c_void_p), ("n_xagg", C.c_uint64)]
+
+
+MEM_DEVICE, MEM_HOST = 1, 2
+
+
 class Timing(C.Structure):
     _fields_ = [("ms", C.c_float * NKERNEL), ("total_ms", C.c_float)]
 
@@ -69,6 +79,41 @@ class BrcError(RuntimeError):
     pass
 
 
+def _load(path):
+    """CDLL(path), and for a HIP build (lib*_hip*.so) one HIP runtime for the whole process first.
+
+    A PyTorch-ROCm wheel carries its own libamdhip64.so / libhsa-runtime64.so and asks for them by a name (libamdhip64.so) that an
+    already loaded system runtime (soname libamdhip64.so.N) does not answer to: with an engine loaded BEFORE torch the process would hold
+    two runtimes, the second finds no GPU ("No HIP GPUs are available"), and a tensor could never meet a brc_device_view.  The other
+    order is fine — torch's copy carries the soname the HIP libraries here ask for — so that order is made the only one: where an
+    installed torch has a runtime of its own it is loaded first (torch itself is not imported), and the libraries of this package
+    bind to it, as they always did in a process that imported torch first (bench.py)."""
+    if "_hip" in os.path.basename(path):
+        _share_torch_hip_runtime()
+    return C.CDLL(path)
+
+
+_torch_hip_runtime = None
+
+
+def _share_torch_hip_runtime():
+    global _torch_hip_runtime
+    import sys
+    if _torch_hip_runtime is not None or "torch" in sys.modules:       # (an imported torch has loaded it already)
+        return
+    _torch_hip_runtime = False
+    import importlib.util
+    try:
+        spec = importlib.util.find_spec("torch")
+    except (ImportError, ValueError):
+        spec = None
+    for d in (spec.submodule_search_locations or []) if spec is not None else []:
+        rt = os.path.join(d, "lib", "libamdhip64.so")
+        if os.path.exists(rt):
+            _torch_hip_runtime = C.CDLL(rt, mode=C.RTLD_GLOBAL)
+            return
+
+
 class Library:
     """One loaded shared library exporting the brc C-ABI."""
 
@@ -76,7 +121,7 @@ class Library:
         if not os.path.exists(path):
             raise BrcError("brc library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
         self.path = path
-        self.lib = L = C.CDLL(path)
+        self.lib = L = _load(path)
         L.brc_strerror.restype = C.c_char_p; L.brc_strerror.argtypes = [C.c_int]
         L.brc_last_error.restype = C.c_char_p; L.brc_last_error.argtypes = [C.c_void_p]
         L.brc_kernel_name.restype = C.c_char_p; L.brc_kernel_name.argtypes = [C.c_int]
@@ -113,6 +158,8 @@ class Library:
         L.brc_format_window.argtypes = [C.c_void_p, C.POINTER(Result), C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
         if hasattr(L, "brc_region_windows"):
             L.brc_region_windows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]
+        if hasattr(L, "brc_device_view_get"):   # (the engine libraries; the checkers have dense results only)
+            L.brc_device_view_get.argtypes = [C.c_void_p, C.POINTER(DeviceView)]
 
     def kind(self):
         return self.lib.brc_engine_kind().decode()
@@ -341,6 +388,13 @@ class Engine:
         self._check(self.L.lib.brc_region_counts(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def device_view(self):
+        """brc_device_view_get: the compact results of the last compute where they lie (a DeviceView; valid until the next
+        begin_region / upload / close of this engine)."""
+        v = DeviceView()
+        self._check(self.L.lib.brc_device_view_get(self.h, C.byref(v)))
+        return v
+
     def piece_steps(self):
         """(ranged, walked) piece-steps of the last compute (brc_region_piece_steps); (0, 0) when the region was not compacted"""
         a, b = C.c_uint64(), C.c_uint64()
@@ -502,7 +556,7 @@ class Inflater:
         if not os.path.exists(path):
             raise BrcError("inflater library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
         self.path = path
-        self.lib = L = C.CDLL(path)
+        self.lib = L = _load(path)
         L.brc_inflater_kind.restype = C.c_char_p
         L.brc_inflater_last_error.restype = C.c_char_p; L.brc_inflater_last_error.argtypes = [C.c_void_p]
         L.brc_inflater_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
@@ -598,7 +652,7 @@ class Deflater:
         if not os.path.exists(path):
             raise BrcError("deflater library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
         self.path = path
-        self.lib = L = _bind_deflate(C.CDLL(path))
+        self.lib = L = _bind_deflate(_load(path))
         h = C.c_void_p()
         rc = L.brc_deflater_create(device, C.byref(h))
         if rc != 0:
@@ -656,3 +710,74 @@ class Deflater:
         k = C.c_double(); c = C.c_double(); bi = C.c_uint64(); bo = C.c_uint64()
         self.lib.brc_deflater_last_timing(self.h, C.byref(k), C.byref(c), C.byref(bi), C.byref(bo))
         return dict(kernel_s=k.value, call_s=c.value, bytes_in=bi.value, bytes_out=bo.value)
+
+
+# ---------------------------------------------------------------- device-resident results (include/brc_dense.h)
+DENSE_LIB = os.path.join(HERE, "csrc", "libbrc_dense_hip.so")
+DENSE_EXPORTS = [
+    "brc_dense_create", "brc_dense_destroy", "brc_dense_kind", "brc_dense_last_error", "brc_dense_expand", "brc_dense_last_timing",
+]
+NMETRIC = 13
+M_NAMES = ["count", "avg_mapq", "avg_bq", "avg_se_mapq", "plus", "minus", "avg_pos", "avg_nm", "avg_mmq", "nq2", "avg_q2_dist",
+           "avg_clipped", "avg_3p"]
+
+
+class Dense:
+    """One handle of a library exporting include/brc_dense.h: the product's libbrc_dense_hip.so (default; raises when it is not built
+    or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_dense).  expand() takes
+    raw addresses; bam_readcount_amd.tensors.region() is the interface that allocates and returns arrays."""
+
+    def __init__(self, path=None, device=0):
+        path = path or DENSE_LIB
+        if not os.path.exists(path):
+            raise BrcError("dense library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
+        self.path = path
+        self.lib = L = _load(path)
+        for s in DENSE_EXPORTS:
+            if not hasattr(L, s):
+                raise BrcError("%s does not export %s" % (path, s))
+        L.brc_dense_kind.restype = C.c_char_p
+        L.brc_dense_last_error.restype = C.c_char_p; L.brc_dense_last_error.argtypes = [C.c_void_p]
+        L.brc_dense_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.brc_dense_destroy.argtypes = [C.c_void_p]; L.brc_dense_destroy.restype = None
+        L.brc_dense_expand.argtypes = [C.c_void_p, C.POINTER(DeviceView), C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7
+        L.brc_dense_last_timing.restype = None
+        L.brc_dense_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self.device = device
+        h = C.c_void_p()
+        rc = L.brc_dense_create(device, C.byref(h))
+        if rc != 0:
+            e = BrcError("brc_dense_create failed: %d" % rc)
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def kind(self):
+        return self.lib.brc_dense_kind().decode()
+
+    def close(self):
+        if self.h:
+            self.lib.brc_dense_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def expand_raw(self, view, k0, n, dst_stride, ncol=None, depth=None, unavail=None, istat=None, fstat=None, metrics=None, stream=None):
+        """brc_dense_expand as it is: destinations are addresses (or None) in memory of the view's kind; returns the code."""
+        return self.lib.brc_dense_expand(self.h, C.byref(view) if view is not None else None, k0, n, dst_stride,
+                                         ncol, depth, unavail, istat, fstat, metrics, stream)
+
+    def expand(self, view, k0, n, dst_stride, **kw):
+        rc = self.expand_raw(view, k0, n, dst_stride, **kw)
+        if rc != 0:
+            raise BrcError("brc_dense_expand: %d (%s)" % (rc, self.lib.brc_dense_last_error(self.h).decode()))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last expand), bytes read and written"""
+        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
+        self.lib.brc_dense_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
+        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)

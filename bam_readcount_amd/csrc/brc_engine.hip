@@ -2906,6 +2906,16 @@ class HipBackend : public Backend {
         if (p) *p = h_ctr.n_positions;
         return BRC_OK;
     }
+    // brc_device_view_get: the planes and the folded third-allele records in HBM, as the last pass left them (every pass has been
+    // waited for); one record per compacted event at the most, the unused ones marked k == NONE32
+    int device_view(brc_device_view* out) override {
+        if (!computed) { err = "not computed"; return BRC_E_ARG; }
+        out->memory = BRC_MEM_DEVICE; out->device = device;
+        out->ncol = (const uint32_t*)d_ncol.p; out->depth = (const uint32_t*)d_depth.p; out->slotid = (const uint32_t*)d_slotid.p;
+        out->si = (const uint32_t*)d_si.p; out->sf = (const float*)d_sf.p; out->unavail = (const uint32_t*)d_unavail.p;
+        out->xagg = d_xagg.p; out->n_xagg = h_ctr.n_xev;
+        return BRC_OK;
+    }
 
     // brc_fetch_window: the compact planes of plane indices [k0, k0 + n) -> pinned window buffers (strided copies: a plane
     // row of n elements out of every PS), the region's two lists whole (downloaded once per computed region)

@@ -1073,6 +1073,19 @@ int brc_region_piece_steps(brc_engine* e, uint64_t* ranged, uint64_t* walked) {
     return BRC_OK;
 }
 
+int brc_device_view_get(brc_engine* e, brc_device_view* out) {
+    if (!e || !out) return BRC_E_ARG;
+    if (e->state < 3) return fail(e, BRC_E_ARG, "brc_device_view_get before brc_compute");
+    brc_device_view v; memset(&v, 0, sizeof v);
+    const int rc = e->be->device_view(&v);
+    if (rc) return fail(e, rc, e->be->last_error());
+    const Geometry& g = e->g;
+    v.n_lib = g.Lp; v.pos0 = g.pos0; v.n_pos = g.P; v.stride = g.PS;
+    if (!e->cfg.per_lib) v.unavail = NULL;
+    *out = v;
+    return BRC_OK;
+}
+
 int brc_clear_indel_queue(brc_engine* e) {
     if (!e) return BRC_E_ARG;
     for (size_t l = 0; l < e->queue.size(); ++l) e->queue[l].clear();

@@ -162,6 +162,17 @@ class Backend {
     virtual int text_wait(int slot, HostText* out) = 0;
     virtual int reserve_text(size_t) { return BRC_OK; }
     virtual void list_sizes(uint64_t* n_xev, uint64_t* n_indel_slots) { *n_xev = 0; *n_indel_slots = 0; }   // of the last compute                                  // room for the text of coming regions (optional)
+    // brc_device_view_get: the compact results of the last compute where they lie (the caller fills in the geometry).  Default: a
+    // backend without device memory of its own hands out what its fetch() returns — host pointers; the HIP backend overrides it
+    // with its device buffers, nothing copied.
+    virtual int device_view(brc_device_view* out) {
+        HostPlanes hp;
+        const int rc = fetch(&hp, true); if (rc) return rc;
+        out->memory = BRC_MEM_HOST; out->device = 0;
+        out->ncol = hp.ncol; out->depth = hp.depth; out->slotid = hp.slotid; out->si = hp.si; out->sf = hp.sf; out->unavail = hp.unavail;
+        out->xagg = hp.xagg; out->n_xagg = hp.n_xagg;
+        return BRC_OK;
+    }
     virtual int counts(uint64_t* n_events, uint64_t* n_positions) = 0;
     // piece-steps of the last compute: what the tile ranges hold / what the pileup kernel walked (0, 0: not counted — no compaction ran)
     virtual void piece_steps(uint64_t* ranged, uint64_t* walked) { *ranged = 0; *walked = 0; }

@@ -302,6 +302,30 @@ int  brc_compute_n(brc_engine*, int32_t n, brc_timing* timing);
  */
 int  brc_fetch_window(brc_engine*, int32_t beg0, int32_t end, brc_result* out);
 
+/*
+ * The last computed region WHERE IT LIES — the results of every pileup_func callback of the region (bamreadcount.cpp:265-419) in the
+ * engine's compact form, not copied anywhere: for a consumer that runs on the device itself (include/brc_dense.h expands such a view
+ * to the dense planes of brc_result, and to the thirteen printed columns, in caller-owned device memory).  `memory` says where the
+ * pointers live: BRC_MEM_DEVICE for the HIP engine (its HBM buffers on HIP device `device`), BRC_MEM_HOST for an engine whose backend
+ * computes in host memory (the CPU lane simulator of the tests).  The planes are struct Planes of brc_core.h: ncol / depth / slotid
+ * [Lp][stride], si [Lp][2][9][stride], sf [Lp][2][4][stride], unavail [stride] (NULL in all-lib mode); xagg: n_xagg records of 64 bytes
+ * (struct XAgg: k, library << 8 | bucket, 9 integers, 4 floats, a pad word), a record whose k is 0xFFFFFFFF is unused.
+ * Valid after a successful brc_compute / brc_compute_n (BRC_E_ARG before), with or without BRC_OPT_TEXT_ONLY / BRC_OPT_DEVICE_TEXT,
+ * before or after brc_fetch_result; the pointers stay valid — and their contents unchanged — until the next brc_begin_region,
+ * brc_upload or brc_destroy of this engine (a brc_compute over the same upload rewrites the same values).  The compute has been
+ * waited for: work on any stream may read them at once.  Indel buckets are not part of the view (brc_fetch_result returns them).
+ */
+#define BRC_MEM_DEVICE 1
+#define BRC_MEM_HOST   2
+typedef struct brc_device_view {
+    int32_t memory;          /* BRC_MEM_DEVICE | BRC_MEM_HOST: where the pointers below live */
+    int32_t device;          /* HIP ordinal (BRC_MEM_DEVICE) */
+    int32_t n_lib, pos0; int64_t n_pos, stride;          /* Lp, pos0, P, PS as in brc_result */
+    const uint32_t *ncol, *depth, *slotid, *si, *unavail; const float* sf;   /* struct Planes, brc_core.h */
+    const void* xagg; uint64_t n_xagg;                   /* XAgg[n_xagg], 64 bytes each; k == 0xFFFFFFFF: unused */
+} brc_device_view;
+int  brc_device_view_get(brc_engine*, brc_device_view* out);   /* after brc_compute / brc_compute_n */
+
 /* Forget deletions queued for pos+1 (d.indel_queue_map.clear(), bamreadcount.cpp:605: after every -l line,
  * NOT between command-line regions).  The queue lives in the host-side assembler (brc_format_region). */
 int  brc_clear_indel_queue(brc_engine*);
