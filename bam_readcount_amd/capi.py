@@ -586,9 +586,10 @@ class Inflater:
         except Exception:
             pass
 
-    def inflate_raw(self, src, dst_cap=None, capacity=None):
+    def inflate_raw(self, src, dst_cap=None, capacity=None, whole=False):
         """brc_inflate_bgzf as it is: (rc, bytes of dst, dst_off[0..n], statuses[0..n)).  dst_cap / capacity None: sized by a first,
-        size-only call.  dst is pre-filled with 0xA5 (what a failed member's slot must still hold afterwards)."""
+        size-only call.  dst is pre-filled with 0xA5 (what a failed member's slot must still hold afterwards); whole: all dst_cap
+        bytes of it come back, not only the members' slots."""
         src = bytes(src)
         sbuf = np.frombuffer(src, np.uint8) if src else np.zeros(1, np.uint8)
         cap = len(src) // 26 + 1 if capacity is None else capacity
@@ -603,7 +604,7 @@ class Inflater:
         k = n.value
         if k > cap:
             return rc, b"", np.zeros(0, np.uint64), np.zeros(0, np.uint8), k
-        return rc, dst[:min(dst_cap, int(off[k]))].tobytes(), off[:k + 1].copy(), st[:k].copy(), k
+        return rc, dst[:dst_cap if whole else min(dst_cap, int(off[k]))].tobytes(), off[:k + 1].copy(), st[:k].copy(), k
 
     def inflate(self, src):
         """Raw BGZF bytes (whole members back to back) -> (inflated bytes, offsets (n + 1), statuses (n)).  Raises when src is not a

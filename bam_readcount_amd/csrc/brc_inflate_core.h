@@ -331,7 +331,8 @@ BRCI_HD int inflate_member(Shared& sh, const uint8_t* src, uint32_t clen, uint8_
 #if defined(__HIP_DEVICE_COMPILE__)
                 *(uint4*)o = make_uint4(x[0], x[1], x[2], x[3]);
 #else
-                o[0] = x[0]; o[1] = x[1]; o[2] = x[2]; o[3] = x[3];
+                typedef uint32_t v4 __attribute__((vector_size(16)));                 // (the host's 16-byte store asks for the same alignment:
+                *(v4*)o = v4{x[0], x[1], x[2], x[3]};                                  //  a wrong `head` is a sanitizer report there too)
 #endif
             }
             if (tail0 + (uint32_t)l < isize) dst[tail0 + l] = sh.win[tail0 + l];

@@ -49,7 +49,8 @@ const char* brc_inflater_last_error(const brc_inflater* h);
  * the BC subfield ... CRC32, ISIZE).  The host walks the BSIZE chain and reads each ISIZE.
  *   *n_members  in: the capacity of status[] (dst_off[] has one entry more); out: the members found.
  *   dst_off[i]  prefix sum of ISIZE: member i's bytes are dst[dst_off[i], dst_off[i + 1]); a BAD_HEADER member takes no room.
- *   status[i]   BRC_INF_*; the slot of a member that failed is left as it was (nothing partial is written).
+ *   status[i]   BRC_INF_*; the slot of a member that failed is left as it was (nothing partial is written).  Payload bytes behind
+ *               the final deflate block are ignored: ISIZE and CRC32 decide, the member is ok (as with both of htslib's back ends).
  * Returns BRC_OK when the call itself ran, whatever the members' statuses.  BRC_E_ARG: dst_cap is below dst_off[n] or the
  * capacity below n (both are still reported, nothing is inflated), or src is not a chain of whole members — a header without
  * magic or BC subfield, a BSIZE that points beyond src: the whole members in front of it are inflated and reported as usual. */

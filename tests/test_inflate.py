@@ -2,10 +2,17 @@
 ([hip]: libbrc_inflate_hip.so) and lane for lane on the CPU ([sim]: tests/sim_inflate).  The reference is zlib itself
 (zlib.decompress(payload, -15), zlib.crc32); equality is byte for byte.
 
+zlib's COMPRESSOR writes only part of what RFC 1951 allows (never a block without a distance code or with a single one, never a run of
+code lengths across the two tables, ...), so next to the members it makes stand streams written WITHOUT it: by the hand encoder of
+tools/fuzz/inflate_members.py (handmade_cases: a fixed list at the format's corners and at the decoder's own boundaries; random_valid: a
+seeded generator).  The reference for those is zlib's DECODER: every such stream must first be accepted by zlib.decompressobj(-15) and
+give the bytes the builder meant ("builder wrong" otherwise), then the inflater must give the same bytes.
+
 The malformed members are a fixed list, each with the status the FORMAT demands (RFC 1951 / RFC 1952 / SAMv1 4.1; the reasoning
 stands next to each case).  They are error paths of a total decoder: the list first runs on the CPU build under the host sanitizers
 (every step outside a member's payload or slot would be a report), then on the plain CPU build, then — the identical list, once — on
-the GPU.  The random-corruption fuzz runs under the sanitizers only."""
+the GPU.  The random-corruption fuzz runs under the sanitizers only; the random valid streams run there first, then a part of them
+through [sim] and [hip]."""
 import os
 import struct
 import subprocess
@@ -139,7 +146,7 @@ def _run_asan(cases, tmp_path):
 
 def test_malformed_members_under_the_host_sanitizers(tmp_path):
     cases = im.malformed_cases()
-    assert len(cases) >= 13
+    assert len(cases) >= 30 and set(im.HANDMADE_MALFORMED) <= {c.name for c in cases}
     for case, (rc, n, st, out) in zip(cases, _run_asan([c.chain for c in cases], tmp_path)):
         _check_case(case, rc, n, st, out)
 
@@ -150,6 +157,122 @@ def test_malformed_members(inflater):
     for case in im.malformed_cases():
         rc, out, off, st, n = inflater.inflate_raw(case.chain)
         _check_case(case, rc, n, st, out)
+
+
+def test_added_malformed_cases_are_refused_by_zlib():
+    """The hand-built malformed streams of the list (im.handmade_malformed) are what they claim to be: zlib's decoder refuses each —
+    it raises, or, for the stream without a final block, never reaches the end — and each expects the status the format demands."""
+    cases = {c.name: c for c in im.malformed_cases()}
+    assert len(im.HANDMADE_MALFORMED) == 12
+    for name in im.HANDMADE_MALFORMED:
+        case = cases[name]
+        assert case.status == [0, im.TRUNCATED if name == "no_final_block" else im.BAD_STREAM, 0], name
+        raw = im.payload_of(im.split_members(case.chain, decode=False)[0][1])
+        d = zlib.decompressobj(-15)
+        try:
+            d.decompress(raw)
+        except zlib.error:
+            continue
+        assert not d.eof, ("builder wrong: zlib takes it", name)
+
+
+def _members_checked_by_zlib(cases):
+    """(name, raw deflate, the bytes the builder meant) -> members, after zlib's decoder has agreed with the builder about every one"""
+    members = []
+    for name, raw, want in cases:
+        d = zlib.decompressobj(-15)
+        try:
+            got = d.decompress(raw)
+        except zlib.error as e:
+            raise AssertionError(("builder wrong: zlib refuses it", name, str(e)))
+        assert d.eof and got == want, ("builder wrong", name, d.eof, len(got), len(want))
+        assert d.unused_data == (raw[-3:] if name == im.TRAILING else b""), ("builder wrong", name)
+        m = im.wrap(raw, zlib.crc32(got), len(got))
+        assert m is not None, ("builder wrong: does not fit a member", name)
+        members.append(m)
+    return members
+
+
+def _inflate_and_compare(inflater, names, members, want):
+    out, off, st = inflater.inflate(b"".join(members))
+    assert st.tolist() == [0] * len(members), [(names[i], s) for i, s in enumerate(st.tolist()) if s]
+    assert off.tolist() == np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist()
+    for i, w in enumerate(want):
+        assert out[int(off[i]):int(off[i + 1])] == w, names[i]
+
+
+def test_handmade_valid_streams(inflater):
+    """Valid streams written by hand (im.handmade_cases), none by zlib's compressor: one distance code of one bit, no distance code, the
+    end-of-block code alone, 15-bit codes on both tables, the fewest and the most code-length lengths, runs of code lengths across the
+    two tables (16, 17, 18), every length and distance symbol at both ends of its extra bits, matches over their own output around 64,
+    blocks that end around the token batches, thousands of blocks, stored blocks at every bit offset, bytes behind the final block.
+    zlib's decoder is the reference; all of them in one call, a stride of them one at a time."""
+    cases = im.handmade_cases()
+    names = [c[0] for c in cases]
+    assert len(set(names)) == len(names) >= 28 and im.TRAILING in names
+    want = [c[2] for c in cases]
+    assert {0, 65536} <= {len(w) for w in want}
+    members = _members_checked_by_zlib(cases)
+    _inflate_and_compare(inflater, names, members, want)
+    for name, m, w in list(zip(names, members, want))[::3]:
+        o1, f1, s1 = inflater.inflate(m)
+        assert s1.tolist() == [0] and f1.tolist() == [0, len(w)] and o1 == w, name
+
+
+def test_slot_geometry(inflater):
+    """The CRC32 (ceil(ISIZE / 64) bytes per lane, lanes without bytes) and the store to dst (bytes up to the first 16-byte boundary,
+    16-byte stores, the rest): members of every ISIZE 0..130, 255..257, 4095..4097 behind a leading member of 0..16 bytes, every group a
+    multiple of 16 bytes long, so that every ISIZE up to 48 begins at every offset modulo 16.  (zlib-made members: the decoder is not the
+    subject.)  Bytes equal, dst_off equal, and the 64 bytes of dst behind the last member still hold their fill."""
+    rng = np.random.default_rng(16)
+    sizes = list(range(131)) + [255, 256, 257, 4095, 4096, 4097]
+    want = []
+    for a in range(17):
+        group = [a] + sizes
+        group.append(-sum(group) % 16)
+        want += [rng.integers(65, 81, n, dtype=np.uint8).tobytes() for n in group]
+    members = [im.member(w, 6) for w in want]
+    offs = np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist()
+    assert {(o % 16, len(w)) for o, w in zip(offs, want)} >= {(r, n) for r in range(16) for n in range(49)}
+    total = offs[-1]
+    rc, out, off, st, n = inflater.inflate_raw(b"".join(members), dst_cap=total + 64, whole=True)
+    assert rc == 0 and n == len(members) and not st.any()
+    assert off.tolist() == offs
+    assert len(out) == total + 64 and out[total:] == b"\xa5" * 64
+    for i, w in enumerate(want):
+        assert out[offs[i]:offs[i + 1]] == w, (i, offs[i] % 16, len(w))
+
+
+RANDOM_VALID_SEED = 19510596
+
+
+def _random_valid_checked(count):
+    rv = im.random_valid(RANDOM_VALID_SEED, count)
+    names = ["random_valid_%d" % i for i in range(count)]
+    members = _members_checked_by_zlib([(n, raw, w) for n, (raw, w, _) in zip(names, rv)])      # (fails on the first one zlib does not take)
+    return rv, names, members
+
+
+def test_random_valid_streams_under_the_host_sanitizers(tmp_path):
+    """2000 seeded valid streams of the generator (random complete code sets down to 15 bits and the two incomplete distance sets the
+    format allows, random tokens, random runs in the header), every one accepted by zlib's decoder; eight members to a chain through
+    the sanitizer build: status ok and zlib's bytes.  At least 100 of them each have a lone distance code, no distance code, a run
+    across the two tables."""
+    rv, names, members = _random_valid_checked(2000)
+    for tag in ("lone", "none", "crossing"):
+        assert sum(tag in tags for _, _, tags in rv) >= 100, tag
+    assert max(len(w) for _, w, _ in rv) <= 4096
+    chains = [b"".join(members[i:i + 8]) for i in range(0, len(members), 8)]
+    for k, (rc, n, st, out) in enumerate(_run_asan(chains, tmp_path)):
+        part = rv[8 * k:8 * k + 8]
+        assert rc == 0 and n == len(part) and st == [0] * n, (names[8 * k], rc, n, st)
+        assert out == b"".join(w for _, w, _ in part), names[8 * k]
+
+
+def test_random_valid_streams(inflater):
+    """The first 200 of the same streams in one call."""
+    rv, names, members = _random_valid_checked(200)
+    _inflate_and_compare(inflater, names, members, [w for _, w, _ in rv])
 
 
 def test_random_corruption_fuzz_under_the_host_sanitizers(tmp_path):
