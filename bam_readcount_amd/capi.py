@@ -20,7 +20,7 @@ F_NAMES = ["sev", "sq2", "snm", "s3p"]
 EXPORTS = [
     "brc_strerror", "brc_last_error", "brc_kernel_name", "brc_engine_kind", "brc_create", "brc_destroy",
     "brc_begin_region", "brc_push_reads", "brc_upload", "brc_compute", "brc_fetch_result", "brc_end_region",
-    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows", "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts", "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned", "brc_region_piece_steps", "brc_device_view_get",
+    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows", "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts", "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned", "brc_region_piece_steps", "brc_device_view_get", "brc_device_indels_get",
 ]
 
 
@@ -61,6 +61,13 @@ class DeviceView(C.Structure):
     _fields_ = [("memory", C.c_int32), ("device", C.c_int32), ("n_lib", C.c_int32), ("pos0", C.c_int32), ("n_pos", C.c_int64),
                 ("stride", C.c_int64), ("ncol", C.c_void_p), ("depth", C.c_void_p), ("slotid", C.c_void_p), ("si", C.c_void_p),
                 ("unavail", C.c_void_p), ("sf", C.c_void_p), ("xagg", C.c_void_p), ("n_xagg", C.c_uint64)]
+
+
+class DeviceIndels(C.Structure):
+    """brc_device_indels (include/brc.h): the indel buckets of a computed region where they lie, and what spells their alleles."""
+    _fields_ = [("memory", C.c_int32), ("device", C.c_int32), ("n_lib", C.c_int32), ("pos0", C.c_int32), ("n_pos", C.c_int64),
+                ("slots", C.c_void_p), ("n_slots", C.c_uint64), ("seq4", C.c_void_p), ("seq_off", C.c_void_p), ("l_qseq", C.c_void_p),
+                ("n_reads", C.c_int64), ("ref", C.c_void_p), ("ref_lo", C.c_int64), ("ref_hi", C.c_int64), ("ref_len", C.c_int64)]
 
 
 MEM_DEVICE, MEM_HOST = 1, 2
@@ -160,6 +167,8 @@ class Library:
             L.brc_region_windows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]
         if hasattr(L, "brc_device_view_get"):   # (the engine libraries; the checkers have dense results only)
             L.brc_device_view_get.argtypes = [C.c_void_p, C.POINTER(DeviceView)]
+        if hasattr(L, "brc_device_indels_get"):
+            L.brc_device_indels_get.argtypes = [C.c_void_p, C.POINTER(DeviceIndels)]
 
     def kind(self):
         return self.lib.brc_engine_kind().decode()
@@ -393,6 +402,13 @@ class Engine:
         begin_region / upload / close of this engine)."""
         v = DeviceView()
         self._check(self.L.lib.brc_device_view_get(self.h, C.byref(v)))
+        return v
+
+    def device_indels(self):
+        """brc_device_indels_get: the indel buckets of the last compute where they lie (a DeviceIndels; valid until the next
+        begin_region / upload / close of this engine)."""
+        v = DeviceIndels()
+        self._check(self.L.lib.brc_device_indels_get(self.h, C.byref(v)))
         return v
 
     def piece_steps(self):
@@ -781,4 +797,81 @@ class Dense:
         """kernel seconds (waits for the launches of the last expand), bytes read and written"""
         k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
         self.lib.brc_dense_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
+        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+
+
+# ---------------------------------------------------------------- the device-resident indel table (include/brc_indels.h)
+INDELS_LIB = os.path.join(HERE, "csrc", "libbrc_indels_hip.so")
+INDELS_EXPORTS = [
+    "brc_indels_create", "brc_indels_destroy", "brc_indels_kind", "brc_indels_last_error", "brc_indels_workspace", "brc_indels_gather",
+    "brc_indels_last_timing",
+]
+INDEL_DESTS = ("pos", "lib", "len", "rep_read", "rep_qpos", "istat", "fstat", "metrics", "allele_off", "alleles")
+
+
+class Indels:
+    """One handle of a library exporting include/brc_indels.h: the product's libbrc_indels_hip.so (default; raises when it is not built
+    or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_indels).  gather() takes
+    raw addresses; bam_readcount_amd.tensors.indels() is the interface that allocates and returns arrays."""
+
+    def __init__(self, path=None, device=0):
+        path = path or INDELS_LIB
+        if not os.path.exists(path):
+            raise BrcError("indels library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
+        self.path = path
+        self.lib = L = _load(path)
+        for s in INDELS_EXPORTS:
+            if not hasattr(L, s):
+                raise BrcError("%s does not export %s" % (path, s))
+        L.brc_indels_kind.restype = C.c_char_p
+        L.brc_indels_last_error.restype = C.c_char_p; L.brc_indels_last_error.argtypes = [C.c_void_p]
+        L.brc_indels_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.brc_indels_destroy.argtypes = [C.c_void_p]; L.brc_indels_destroy.restype = None
+        L.brc_indels_workspace.restype = C.c_size_t; L.brc_indels_workspace.argtypes = [C.POINTER(DeviceIndels), C.c_int64]
+        L.brc_indels_gather.argtypes = ([C.c_void_p, C.POINTER(DeviceIndels), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int64] +
+                                        [C.c_void_p] * 11)
+        L.brc_indels_last_timing.restype = None
+        L.brc_indels_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self.device = device
+        h = C.c_void_p()
+        rc = L.brc_indels_create(device, C.byref(h))
+        if rc != 0:
+            e = BrcError("brc_indels_create failed: %d" % rc)
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def kind(self):
+        return self.lib.brc_indels_kind().decode()
+
+    def close(self):
+        if self.h:
+            self.lib.brc_indels_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace(self, view, n):
+        """bytes of scratch a gather over n positions of the view needs"""
+        return int(self.lib.brc_indels_workspace(C.byref(view) if view is not None else None, n))
+
+    def gather_raw(self, view, k0, n, workspace=None, workspace_bytes=0, counts=None, cap=0, alleles_cap=0, pos=None, lib=None, len=None,
+                   rep_read=None, rep_qpos=None, istat=None, fstat=None, metrics=None, allele_off=None, alleles=None, stream=None):
+        """brc_indels_gather as it is: scratch and destinations are addresses (or None) in memory of the view's kind; returns the code."""
+        return self.lib.brc_indels_gather(self.h, C.byref(view) if view is not None else None, k0, n, workspace, workspace_bytes, counts,
+                                          cap, alleles_cap, pos, lib, len, rep_read, rep_qpos, istat, fstat, metrics, allele_off, alleles, stream)
+
+    def gather(self, view, k0, n, **kw):
+        rc = self.gather_raw(view, k0, n, **kw)
+        if rc != 0:
+            raise BrcError("brc_indels_gather: %d (%s)" % (rc, self.lib.brc_indels_last_error(self.h).decode()))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last gather), bytes read and written"""
+        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
+        self.lib.brc_indels_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
         return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)

@@ -2916,6 +2916,17 @@ class HipBackend : public Backend {
         out->xagg = d_xagg.p; out->n_xagg = h_ctr.n_xev;
         return BRC_OK;
     }
+    // brc_device_indels_get: k_indel_reduce's records in HBM (one slot per indel event at the most, the unused ones have len == 0)
+    // and the device copies of what spells their alleles — the reads' SEQ as uploaded, the reference slice
+    int device_indels(const Staged&, const Geometry&, brc_device_indels* out) override {
+        if (!computed) { err = "not computed"; return BRC_E_ARG; }
+        const bool indels = n_indel_cap > 0 && c.P > 0 && c.n_reads > 0;
+        out->memory = BRC_MEM_DEVICE; out->device = device;
+        out->n_slots = indels ? h_ctr.n_indel_slots : 0u; out->slots = out->n_slots ? d_iout.p : nullptr;
+        out->seq4 = (const uint8_t*)d_seq.p; out->seq_off = (const uint64_t*)d_so.p; out->l_qseq = (const int32_t*)d_lq.p; out->n_reads = c.n_reads;
+        out->ref = c.has_ref ? (const char*)d_ref.p : nullptr;
+        return BRC_OK;
+    }
 
     // brc_fetch_window: the compact planes of plane indices [k0, k0 + n) -> pinned window buffers (strided copies: a plane
     // row of n elements out of every PS), the region's two lists whole (downloaded once per computed region)

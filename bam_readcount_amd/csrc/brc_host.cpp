@@ -1086,6 +1086,20 @@ int brc_device_view_get(brc_engine* e, brc_device_view* out) {
     return BRC_OK;
 }
 
+int brc_device_indels_get(brc_engine* e, brc_device_indels* out) {
+    if (!e || !out) return BRC_E_ARG;
+    if (e->state < 3) return fail(e, BRC_E_ARG, "brc_device_indels_get before brc_compute");
+    brc_device_indels v; memset(&v, 0, sizeof v);
+    const int rc = e->be->device_indels(e->st, e->g, &v);
+    if (rc) return fail(e, rc, e->be->last_error());
+    const Geometry& g = e->g;
+    v.n_lib = g.Lp; v.pos0 = g.pos0; v.n_pos = g.P;
+    v.ref_lo = g.ref_lo; v.ref_hi = g.ref_hi; v.ref_len = g.ref_len;
+    if (!v.n_slots) v.slots = NULL;
+    *out = v;
+    return BRC_OK;
+}
+
 int brc_clear_indel_queue(brc_engine* e) {
     if (!e) return BRC_E_ARG;
     for (size_t l = 0; l < e->queue.size(); ++l) e->queue[l].clear();

@@ -173,6 +173,19 @@ class Backend {
         out->xagg = hp.xagg; out->n_xagg = hp.n_xagg;
         return BRC_OK;
     }
+    // brc_device_indels_get: the reduced indel buckets of the last compute and the inputs that spell their alleles, where they lie
+    // (the caller fills in the geometry).  Default: the list of the backend's own fetch() and the staged host arrays — for a backend
+    // whose "device" pointers ARE the staging arrays (it does not adopt arenas); the HIP backend overrides it with d_iout and the
+    // device copies of the inputs.
+    virtual int device_indels(const Staged& s, const Geometry& g, brc_device_indels* out) {
+        HostPlanes hp;
+        const int rc = fetch(&hp, false); if (rc) return rc;
+        out->memory = BRC_MEM_HOST; out->device = 0;
+        out->slots = hp.n_indel ? hp.indel : nullptr; out->n_slots = (uint64_t)hp.n_indel;
+        out->seq4 = s.seq4.p; out->seq_off = s.seq_off.p; out->l_qseq = s.l_qseq.p; out->n_reads = s.n;
+        out->ref = g.ref ? g.ref + g.ref_lo : nullptr;
+        return BRC_OK;
+    }
     virtual int counts(uint64_t* n_events, uint64_t* n_positions) = 0;
     // piece-steps of the last compute: what the tile ranges hold / what the pileup kernel walked (0, 0: not counted — no compaction ran)
     virtual void piece_steps(uint64_t* ranged, uint64_t* walked) { *ranged = 0; *walked = 0; }

@@ -16,7 +16,7 @@ Lifetime: region() reads the engine's buffers of the LAST compute.  With the HIP
 queued, so the next begin_region / upload / close of that engine must not start before they have run — synchronise the stream
 (or use the results on the host, which does) first.  The returned arrays are the caller's and stay valid.
 
-Indel buckets are not part of these arrays; engine.fetch_result() returns them (on a text_only engine without any planes).
+Indel buckets are not part of region()'s arrays: indels() below returns them as a sorted table, in the same memory.
 """
 import numpy as np
 
@@ -106,3 +106,71 @@ def _torch_arrays(shp, want, out, device):
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream().cuda_stream
     return arrays, (lambda a: a.data_ptr()), stream
+
+
+INDEL_KINDS = capi.INDEL_DESTS
+INDEL_DEFAULT_WANT = INDEL_KINDS
+
+
+def indel_shapes(m, allele_bytes):
+    """kind -> (shape, numpy dtype) of a table of m records: record r is element r of the last axis"""
+    return {"pos": ((m,), np.int32), "lib": ((m,), np.int32), "len": ((m,), np.int32), "rep_read": ((m,), np.uint32), "rep_qpos": ((m,), np.int32),
+            "istat": ((capi.NI, m), np.uint32), "fstat": ((capi.NF, m), np.float32), "metrics": ((capi.NMETRIC, m), np.float32),
+            "allele_off": ((m + 1,), np.uint32), "alleles": ((allele_bytes,), np.uint8)}
+
+
+def indels(engine, indels, beg0=None, end=None, want=INDEL_DEFAULT_WANT):
+    """The indel buckets of the engine's last computed region whose position lies in [beg0, end) (clipped to the region's positions as
+    region() clips), in brc_result.indel's order: ascending (position, library, allele text) — include/brc_indels.h.
+
+    Returns a dict: every kind in `want` (INDEL_KINDS) -> an array shaped as in indel_shapes(): pos, lib, len, rep_read, rep_qpos [m],
+    istat [9, m], fstat [4, m], metrics [13, m], allele_off [m + 1], alleles (uint8: the text of record r is
+    alleles[allele_off[r]:allele_off[r + 1]], sign first), plus the ints "m" (records), "first" and "n" (the window).
+    With the HIP libraries the arrays are torch tensors on the engine's device, filled on torch's current stream, the scratch comes
+    from torch.empty; with the CPU builds they are numpy arrays.
+
+    SYNCHRONISES ONCE: the table's sizes are data.  A first gather asks for the two counts alone, the host reads them (as
+    torch.nonzero does), then the arrays are allocated exactly and a second gather fills them without another wait.
+    """
+    want = tuple(want)
+    for k in want:
+        if k not in INDEL_KINDS:
+            raise ValueError("unknown kind %r (one of %r)" % (k, INDEL_KINDS))
+    v = engine.device_indels()
+    P, pos0 = int(v.n_pos), int(v.pos0)
+    lo = pos0 if beg0 is None else max(int(beg0), pos0)
+    hi = pos0 + P if end is None else min(int(end), pos0 + P)
+    lo = min(lo, pos0 + P)
+    n = max(hi - lo, 0)
+    k0 = lo - pos0 if n else 0
+    wsb = indels.workspace(v, n)
+    if v.memory == capi.MEM_HOST:
+        def empty(shape, dt):
+            return np.empty(shape, dt)
+        ptr, stream = (lambda a: a.ctypes.data), None
+        ws = np.empty(max(wsb // 4, 1), np.uint32)
+        counts = np.zeros(2, np.uint32)
+    elif v.memory == capi.MEM_DEVICE:
+        import torch          # (lazily: the package and its CPU route work without torch)
+        dev = torch.device("cuda", int(v.device))
+        tdt = {np.int32: torch.int32, np.uint32: torch.uint32, np.float32: torch.float32, np.uint8: torch.uint8}
+
+        def empty(shape, dt):
+            return torch.empty(shape, dtype=tdt[dt], device=dev)
+        ptr = lambda a: a.data_ptr()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+        ws = torch.empty(max(wsb // 4, 1), dtype=torch.int32, device=dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    else:
+        raise capi.BrcError("brc_device_indels of unknown memory kind %d" % v.memory)
+    indels.gather(v, k0, n, workspace=ptr(ws), workspace_bytes=wsb, counts=ptr(counts), stream=stream)
+    m, nbytes = (int(x) & 0xFFFFFFFF for x in (counts.tolist() if v.memory == capi.MEM_HOST else counts.cpu().tolist()))      # the one wait
+    shp = indel_shapes(m, nbytes)
+    arrays = {k: empty(*shp[k]) for k in want}
+    if want:
+        indels.gather(v, k0, n, workspace=ptr(ws), workspace_bytes=wsb, cap=m, alleles_cap=nbytes, stream=stream,
+                      **{k: ptr(arrays[k]) for k in want})
+    res = {"m": m, "first": pos0 + k0, "n": n}
+    res.update(arrays)
+    return res

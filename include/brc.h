@@ -313,7 +313,7 @@ int  brc_fetch_window(brc_engine*, int32_t beg0, int32_t end, brc_result* out);
  * Valid after a successful brc_compute / brc_compute_n (BRC_E_ARG before), with or without BRC_OPT_TEXT_ONLY / BRC_OPT_DEVICE_TEXT,
  * before or after brc_fetch_result; the pointers stay valid — and their contents unchanged — until the next brc_begin_region,
  * brc_upload or brc_destroy of this engine (a brc_compute over the same upload rewrites the same values).  The compute has been
- * waited for: work on any stream may read them at once.  Indel buckets are not part of the view (brc_fetch_result returns them).
+ * waited for: work on any stream may read them at once.  Indel buckets have a view of their own: brc_device_indels_get below.
  */
 #define BRC_MEM_DEVICE 1
 #define BRC_MEM_HOST   2
@@ -325,6 +325,44 @@ typedef struct brc_device_view {
     const void* xagg; uint64_t n_xagg;                   /* XAgg[n_xagg], 64 bytes each; k == 0xFFFFFFFF: unused */
 } brc_device_view;
 int  brc_device_view_get(brc_engine*, brc_device_view* out);   /* after brc_compute / brc_compute_n */
+
+/*
+ * The INDEL buckets of the last computed region where they lie (LibraryCounts::indel_stats, bamreadcount.cpp:47,315-342) — the
+ * second half of the view above, for the same kind of consumer: include/brc_indels.h turns it into brc_result.indel's sorted table
+ * (position, library, allele text; the 13 accumulators, the 13 printed columns, the allele text) in caller-owned memory of the same
+ * kind.  Plain data, nothing copied; the same validity window as brc_device_view (after a successful brc_compute / brc_compute_n —
+ * BRC_E_ARG before —, with or without BRC_OPT_TEXT_ONLY / BRC_OPT_DEVICE_TEXT, before or after brc_fetch_result, until the next
+ * brc_begin_region / brc_upload / brc_destroy of this engine), and `memory` / `device` mean what they mean there.
+ *   slots     n_slots records of 72 bytes, in UNSPECIFIED order (struct IndelOut of brc_core.h):
+ *                 int32 pos        0-based reference position of the base before the indel (the pileup position)
+ *                 int32 lib        library index (0 in all-lib mode)
+ *                 int32 len        > 0 insertion length, < 0 deletion length, 0: THE RECORD IS UNUSED
+ *                 uint32 rep_read  region-wide index (push order) of the first read carrying the allele
+ *                 int32 rep_qpos   qpos of that read at pos: the inserted bases are its bases rep_qpos + 1 .. rep_qpos + len
+ *                 uint32 i[9]      BRC_I_*
+ *                 float f[4]       BRC_F_*
+ *             one record per (position, library, allele) — the alleles of one (position, library) are distinct.  n_slots == 0 with
+ *             slots == NULL is a valid view (no reference given: no alleles are collected; or no indel in the region).
+ *   What spells an allele (bamreadcount.cpp:324-338) — the pushed reads as they were uploaded, in BAM's own layouts (brc_read_batch;
+ *   offsets rebased to the region), NOT the engine's event-byte stream: that stream is an engine internal whose encoding (escape
+ *   bytes, a sparse wide stream) is no ABI, while seq4 is SAMv1's.
+ *       seq4, seq_off [n_reads], l_qseq [n_reads]   inserted base j of a record: nibble rep_qpos + 1 + j of read rep_read (high nibble
+ *             first) through "=ACGTN" (A C G T N '=' themselves, every other code N); N when that offset is at or past l_qseq
+ *       ref, ref_lo, ref_hi, ref_len   ref[p - ref_lo] is the raw reference character of contig position p for ref_lo <= p < ref_hi
+ *             (the slice the engine uploaded: it covers every pushed read); deleted base j of a record is position pos + 1 + j, N where
+ *             the slice has none (p >= ref_len, outside the slice, a NUL character, ref == NULL).
+ *   For a BRC_MEM_HOST view `ref` points into the caller's own reference (brc_begin_region), which must stay in place as long as the
+ *   view is used.
+ */
+typedef struct brc_device_indels {
+    int32_t memory;          /* BRC_MEM_DEVICE | BRC_MEM_HOST */
+    int32_t device;          /* HIP ordinal (BRC_MEM_DEVICE) */
+    int32_t n_lib, pos0; int64_t n_pos;                  /* Lp, pos0, P as in brc_result */
+    const void* slots; uint64_t n_slots;                 /* 72-byte records, see above; len == 0: unused */
+    const uint8_t* seq4; const uint64_t* seq_off; const int32_t* l_qseq; int64_t n_reads;
+    const char* ref; int64_t ref_lo, ref_hi, ref_len;
+} brc_device_indels;
+int  brc_device_indels_get(brc_engine*, brc_device_indels* out);   /* after brc_compute / brc_compute_n */
 
 /* Forget deletions queued for pos+1 (d.indel_queue_map.clear(), bamreadcount.cpp:605: after every -l line,
  * NOT between command-line regions).  The queue lives in the host-side assembler (brc_format_region). */

@@ -8,8 +8,8 @@
  *
  * What it stands in for: the reference has the BasicStat of every (position, library, base) in memory only while pileup_func prints
  * it (bamreadcount.cpp:351-416, operator<<(BasicStat), BasicStat.cpp:110-159); brc_fetch_result gives a caller the same numbers as
- * host arrays (expand_slots, brc_host.cpp); this gives them to a caller on the GPU.  Indel buckets are not covered: they stay with
- * brc_fetch_result. */
+ * host arrays (expand_slots, brc_host.cpp); this gives them to a caller on the GPU.  Indel buckets are not covered here: include/brc_indels.h
+ * gives them to the same kind of caller (brc_device_indels_get + brc_indels_gather). */
 #ifndef BRC_DENSE_H
 #define BRC_DENSE_H
 
