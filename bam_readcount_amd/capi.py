@@ -875,3 +875,75 @@ class Indels:
         k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
         self.lib.brc_indels_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
         return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+
+
+# ---------------------------------------------------------------- device-resident site panels (include/brc_panel.h)
+PANEL_LIB = os.path.join(HERE, "csrc", "libbrc_panel_hip.so")
+PANEL_EXPORTS = [
+    "brc_panel_create", "brc_panel_destroy", "brc_panel_kind", "brc_panel_last_error", "brc_panel_gather", "brc_panel_last_timing",
+]
+PANEL_OUT_OF_RANGE, PANEL_NOT_ASCENDING = 1, 2
+PANEL_DESTS = ("ncol", "depth", "unavail", "istat", "fstat", "metrics")
+
+
+class Panel:
+    """One handle of a library exporting include/brc_panel.h: the product's libbrc_panel_hip.so (default; raises when it is not built
+    or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_panel).  gather() takes
+    raw addresses; bam_readcount_amd.tensors.sites() is the interface that allocates and returns arrays."""
+
+    def __init__(self, path=None, device=0):
+        path = path or PANEL_LIB
+        if not os.path.exists(path):
+            raise BrcError("panel library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
+        self.path = path
+        self.lib = L = _load(path)
+        for s in PANEL_EXPORTS:
+            if not hasattr(L, s):
+                raise BrcError("%s does not export %s" % (path, s))
+        L.brc_panel_kind.restype = C.c_char_p
+        L.brc_panel_last_error.restype = C.c_char_p; L.brc_panel_last_error.argtypes = [C.c_void_p]
+        L.brc_panel_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.brc_panel_destroy.argtypes = [C.c_void_p]; L.brc_panel_destroy.restype = None
+        L.brc_panel_gather.argtypes = [C.c_void_p, C.POINTER(DeviceView), C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8
+        L.brc_panel_last_timing.restype = None
+        L.brc_panel_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self.device = device
+        h = C.c_void_p()
+        rc = L.brc_panel_create(device, C.byref(h))
+        if rc != 0:
+            e = BrcError("brc_panel_create failed: %d" % rc)
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def kind(self):
+        return self.lib.brc_panel_kind().decode()
+
+    def close(self):
+        if self.h:
+            self.lib.brc_panel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def gather_raw(self, view, idx, n, dst_stride, ncol=None, depth=None, unavail=None, istat=None, fstat=None, metrics=None, status=None,
+                   stream=None):
+        """brc_panel_gather as it is: the list, the destinations and the status word are addresses (or None) in memory of the view's
+        kind; returns the code."""
+        return self.lib.brc_panel_gather(self.h, C.byref(view) if view is not None else None, idx, n, dst_stride,
+                                         ncol, depth, unavail, istat, fstat, metrics, status, stream)
+
+    def gather(self, view, idx, n, dst_stride, **kw):
+        rc = self.gather_raw(view, idx, n, dst_stride, **kw)
+        if rc != 0:
+            raise BrcError("brc_panel_gather: %d (%s)" % (rc, self.lib.brc_panel_last_error(self.h).decode()))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last gather), bytes asked for and written"""
+        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
+        self.lib.brc_panel_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
+        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)

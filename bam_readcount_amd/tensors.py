@@ -17,6 +17,9 @@ queued, so the next begin_region / upload / close of that engine must not start 
 (or use the results on the host, which does) first.  The returned arrays are the caller's and stay valid.
 
 Indel buckets are not part of region()'s arrays: indels() below returns them as a sorted table, in the same memory.
+
+A site list — positions scattered over planes that are otherwise EMPTY (Engine.region_windows) — is served by sites(): the listed
+positions alone, gathered by libbrc_panel_hip.so (capi.Panel) in one call, in the same memory.
 """
 import numpy as np
 
@@ -173,4 +176,133 @@ def indels(engine, indels, beg0=None, end=None, want=INDEL_DEFAULT_WANT):
                       **{k: ptr(arrays[k]) for k in want})
     res = {"m": m, "first": pos0 + k0, "n": n}
     res.update(arrays)
+    return res
+
+
+def _window_positions(windows):
+    """(vbeg0, vend) -> (positions of [vbeg0[i], vend[i]) of every window in order, the window number of each), int64"""
+    if len(windows) != 2:
+        raise ValueError("windows is a pair of arrays (vbeg0, vend)")
+    b = np.asarray(windows[0], np.int64).ravel(); e = np.asarray(windows[1], np.int64).ravel()
+    if b.shape != e.shape or (e < b).any():
+        raise ValueError("windows: vbeg0 and vend must have one length, and no window may end before it begins")
+    cnt = e - b
+    n = int(cnt.sum())
+    site = np.repeat(np.arange(b.size, dtype=np.int64), cnt)
+    pos = np.repeat(b, cnt) + (np.arange(n, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+    return pos, site
+
+
+def sites(engine, panel, positions=None, windows=None, want=DEFAULT_WANT, out=None, indels=None):
+    """The LISTED positions of the engine's last computed region, and nothing else (include/brc_panel.h): for a region whose windows
+    were announced with Engine.region_windows, where every other position is empty and a whole-axis region() would expand them all.
+
+    Exactly one of
+      positions: reference (axis) positions — a sequence, a numpy array, or (HIP libraries) an int32 torch tensor already on the
+                 engine's device;
+      windows:   a pair of arrays (vbeg0, vend), the arrays Engine.region_windows takes: the positions [vbeg0[i], vend[i]) of every
+                 window, in order.
+    A list given on the host is checked on the host — non-decreasing (equal neighbours are fine: site lists repeat lines) and inside
+    the planes, ValueError otherwise, before anything is queued — and uploaded once.  A device tensor is used where it lies and NOT
+    checked; nothing synchronises: "status" tells afterwards (capi.PANEL_OUT_OF_RANGE: such elements are empty positions;
+    capi.PANEL_NOT_ASCENDING: buckets with a third-allele record are unspecified).
+
+    Returns region()'s dict — every kind in `want` -> an array shaped shapes(n_lib, N), element j is listed position j — plus "pos"
+    [N] int32 (the positions), "site" [N] int32 (the window number of each element; arange(N) for `positions`), "status" (one uint32
+    element in the arrays' memory, written by the kernels, not read by this call) and the ints "n", "n_lib", "pos0".
+    out: as for region().
+    indels: a capi.Indels of the engine's kind -> also "indels": indels() over [min, max] of the list (SYNCHRONISES, see there; for a
+    device list also to learn min and max), reduced to the records whose position is listed, each with "j": the index of the first
+    listed element of its position.
+    """
+    if (positions is None) == (windows is None):
+        raise ValueError("give exactly one of positions and windows")
+    want = tuple(want)
+    for k in want:
+        if k not in KINDS:
+            raise ValueError("unknown kind %r (one of %r)" % (k, KINDS))
+    v = engine.device_view()
+    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    if v.memory not in (capi.MEM_HOST, capi.MEM_DEVICE):
+        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
+    on_device = type(positions).__module__.split(".")[0] == "torch"
+    if on_device:
+        if v.memory != capi.MEM_DEVICE:
+            raise ValueError("a torch tensor of positions needs an engine whose results lie on a GPU")
+        n = int(positions.numel())
+    else:
+        pos, site = _window_positions(windows) if windows is not None else (np.asarray(positions, np.int64).ravel(), None)
+        n = int(pos.size)
+        if n and (pos[1:] < pos[:-1]).any():
+            raise ValueError("the listed positions must not descend")
+        if n and (pos[0] < pos0 or pos[-1] >= pos0 + P):
+            raise ValueError("listed positions outside the region's planes [%d, %d)" % (pos0, pos0 + P))
+        if site is None:
+            site = np.arange(n)
+        host = np.stack([pos - pos0, pos, site]).astype(np.int32)          # idx, pos, site: one upload
+    shp = shapes(L, n)
+    if v.memory == capi.MEM_HOST:
+        arrays, ptr, stream = _host_arrays(shp, want, out), (lambda a: a.ctypes.data), None
+        idx, lpos, lsite = host[0], host[1], host[2]
+        status = np.zeros(1, np.uint32)
+    else:
+        arrays, ptr, stream = _torch_arrays(shp, want, out, int(v.device))
+        import torch
+        dev = torch.device("cuda", int(v.device))
+        if on_device:
+            if positions.dtype != torch.int32 or positions.device != dev or positions.dim() != 1 or not positions.is_contiguous():
+                raise ValueError("positions must be a contiguous one-dimensional int32 tensor on %s" % dev)
+            lpos, idx, lsite = positions, positions - pos0, torch.arange(n, dtype=torch.int32, device=dev)
+        else:
+            idx, lpos, lsite = torch.from_numpy(host).to(dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev).view(torch.uint32)
+    if n:
+        panel.gather(v, ptr(idx), n, n, status=ptr(status), stream=stream, **{k: ptr(arrays[k]) for k in want})
+    res = {"pos0": pos0, "n": n, "n_lib": L, "pos": lpos, "site": lsite, "status": status}
+    res.update(arrays)
+    if indels is not None:
+        res["indels"] = _listed_indels(engine, indels, lpos, n, pos0)
+    return res
+
+
+def _listed_indels(engine, indels_lib, listed, n, pos0):
+    """indels() over [min, max] of the listed positions, reduced to the records whose position is listed, plus "j": searchsorted and
+    index arithmetic in numpy / torch, no kernel of its own."""
+    if n == 0:
+        t = indels(engine, indels_lib, beg0=pos0, end=pos0)          # (an empty window: no record)
+    else:
+        t = indels(engine, indels_lib, beg0=int(listed.min()), end=int(listed.max()) + 1)
+    if isinstance(t["pos"], np.ndarray):
+        def take(a, sel):
+            return a[..., sel]
+        rep, cat = np.repeat, np.concatenate
+        off = t["allele_off"].astype(np.int64)
+        as_u32, as_i32 = (lambda a: a.astype(np.uint32)), (lambda a: a.astype(np.int32))
+        arange, zero1 = np.arange, np.zeros(1, np.int64)
+        jj = np.searchsorted(listed, t["pos"], side="left") if n else np.zeros(0, np.int64)
+        sel = np.nonzero((jj < n) & (listed[np.minimum(jj, n - 1)] == t["pos"]))[0] if n else jj
+    else:
+        import torch
+        dev = t["pos"].device
+
+        def take(a, sel):             # (torch indexes no unsigned 32-bit tensors: through their int32 view)
+            if a.dtype == torch.uint32:
+                return a.view(torch.int32).index_select(a.dim() - 1, sel).view(torch.uint32)
+            return a.index_select(a.dim() - 1, sel)
+        rep, cat = torch.repeat_interleave, torch.cat
+        off = t["allele_off"].view(torch.int32).to(torch.int64)
+        as_u32, as_i32 = (lambda a: a.to(torch.int32).view(torch.uint32)), (lambda a: a.to(torch.int32))
+
+        def arange(k):
+            return torch.arange(k, dtype=torch.int64, device=dev)
+        zero1 = arange(1)
+        jj = torch.searchsorted(listed, t["pos"]) if n else torch.zeros(0, dtype=torch.int64, device=dev)
+        sel = ((jj < n) & (listed[jj.clamp(max=n - 1)] == t["pos"])).nonzero().reshape(-1) if n else jj
+    # the kept records' allele text, packed: byte i of the new text comes from the old offset of its record + its place inside it
+    lens = (off[1:] - off[:-1])[sel]
+    new_off = cat([zero1, lens.cumsum(0)])
+    src = rep(off[:-1][sel] - new_off[:-1], lens) + arange(int(new_off[-1]))
+    res = {"first": t["first"], "n": t["n"], "m": int(sel.shape[0]), "j": as_i32(take(jj, sel))}
+    for k in INDEL_KINDS:
+        res[k] = as_u32(new_off) if k == "allele_off" else take(t[k], src if k == "alleles" else sel)
     return res
