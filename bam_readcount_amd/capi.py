@@ -947,3 +947,101 @@ class Panel:
         k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
         self.lib.brc_panel_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
         return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+
+
+# ---------------------------------------------------------------- device-side site selection (include/brc_select.h)
+SELECT_LIB = os.path.join(HERE, "csrc", "libbrc_select_hip.so")
+SELECT_EXPORTS = [
+    "brc_select_create", "brc_select_destroy", "brc_select_kind", "brc_select_last_error", "brc_select_workspace", "brc_select_sites",
+    "brc_select_last_timing",
+]
+SELECT_SNV, SELECT_INDEL = 1, 2
+ROLE_IGNORE, ROLE_CASE, ROLE_CONTROL = 0, 1, 2
+SELECT_MAX_LIB = 254
+WHY_A, WHY_C, WHY_G, WHY_T, WHY_INS, WHY_DEL = 1, 2, 4, 8, 16, 32
+
+
+class SelectParams(C.Structure):
+    """brc_select_params (include/brc_select.h)"""
+    _fields_ = [("role", C.c_void_p), ("flags", C.c_uint32), ("min_depth", C.c_uint32), ("min_alt", C.c_uint32), ("frac_num", C.c_uint32),
+                ("frac_den", C.c_uint32), ("ctl_min_depth", C.c_uint32), ("ctl_max_alt", C.c_uint32), ("ctl_frac_num", C.c_uint32),
+                ("ctl_frac_den", C.c_uint32)]
+
+
+def select_params(role=None, flags=SELECT_SNV | SELECT_INDEL, min_depth=0, min_alt=1, frac=(0, 1), ctl_min_depth=0, ctl_max_alt=2 ** 32 - 1,
+                  ctl_frac=(1, 1)):
+    """(SelectParams, keepalive): role is a sequence of ROLE_* per library, or None (every library a case library)"""
+    p = SelectParams(None, flags, min_depth, min_alt, frac[0], frac[1], ctl_min_depth, ctl_max_alt, ctl_frac[0], ctl_frac[1])
+    keep = None
+    if role is not None:
+        keep = np.ascontiguousarray(role, np.uint8)
+        p.role = keep.ctypes.data
+    return p, keep
+
+
+class Select:
+    """One handle of a library exporting include/brc_select.h: the product's libbrc_select_hip.so (default; raises when it is not built
+    or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_select).  sites() takes
+    raw addresses; bam_readcount_amd.tensors.select() is the interface that allocates and returns arrays."""
+
+    def __init__(self, path=None, device=0):
+        path = path or SELECT_LIB
+        if not os.path.exists(path):
+            raise BrcError("select library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
+        self.path = path
+        self.lib = L = _load(path)
+        for s in SELECT_EXPORTS:
+            if not hasattr(L, s):
+                raise BrcError("%s does not export %s" % (path, s))
+        L.brc_select_kind.restype = C.c_char_p
+        L.brc_select_last_error.restype = C.c_char_p; L.brc_select_last_error.argtypes = [C.c_void_p]
+        L.brc_select_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.brc_select_destroy.argtypes = [C.c_void_p]; L.brc_select_destroy.restype = None
+        L.brc_select_workspace.restype = C.c_int64
+        L.brc_select_workspace.argtypes = [C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.c_int64]
+        L.brc_select_sites.argtypes = ([C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(SelectParams), C.c_int64, C.c_int64, C.c_int64] +
+                                       [C.c_void_p] * 5)
+        L.brc_select_last_timing.restype = None
+        L.brc_select_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self.device = device
+        h = C.c_void_p()
+        rc = L.brc_select_create(device, C.byref(h))
+        if rc != 0:
+            e = BrcError("brc_select_create failed: %d" % rc)
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def kind(self):
+        return self.lib.brc_select_kind().decode()
+
+    def close(self):
+        if self.h:
+            self.lib.brc_select_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def workspace(self, view, indels, n):
+        """bytes of scratch a selection over n positions of the views needs"""
+        return int(self.lib.brc_select_workspace(C.byref(view) if view is not None else None, C.byref(indels) if indels is not None else None, n))
+
+    def sites_raw(self, view, indels, params, k0, n, cap=0, idx=None, why=None, counts=None, workspace=None, stream=None):
+        """brc_select_sites as it is: scratch and destinations are addresses (or None) in memory of the views' kind; returns the code."""
+        return self.lib.brc_select_sites(self.h, C.byref(view) if view is not None else None, C.byref(indels) if indels is not None else None,
+                                         C.byref(params) if params is not None else None, k0, n, cap, idx, why, counts, workspace, stream)
+
+    def sites(self, view, indels, params, k0, n, **kw):
+        rc = self.sites_raw(view, indels, params, k0, n, **kw)
+        if rc != 0:
+            raise BrcError("brc_select_sites: %d (%s)" % (rc, self.lib.brc_select_last_error(self.h).decode()))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last selection), bytes asked for and scratch bytes written"""
+        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
+        self.lib.brc_select_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
+        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)

@@ -20,6 +20,11 @@ Indel buckets are not part of region()'s arrays: indels() below returns them as 
 
 A site list — positions scattered over planes that are otherwise EMPTY (Engine.region_windows) — is served by sites(): the listed
 positions alone, gathered by libbrc_panel_hip.so (capi.Panel) in one call, in the same memory.
+
+The positions worth listing can be picked on the device too: select() returns those with non-reference evidence (a base, an insertion,
+a deletion) in "case" libraries and none in "control" libraries, found by libbrc_select_hip.so (capi.Select) over the compact planes:
+    sel = tensors.select(eng, select, case=["tumor"], control=["normal"], min_depth=10, min_alt=3, min_frac=(1, 20), ctl_max_alt=0)
+    panel = tensors.sites(eng, capi.Panel(), positions=sel["pos"])
 """
 import numpy as np
 
@@ -306,3 +311,109 @@ def _listed_indels(engine, indels_lib, listed, n, pos0):
     for k in INDEL_KINDS:
         res[k] = as_u32(new_off) if k == "allele_off" else take(t[k], src if k == "alleles" else sel)
     return res
+
+
+def _roles(engine, n_lib, role, case, control):
+    """role (a sequence of capi.ROLE_* per library) or case= / control= (library names of the engine) -> uint8 [n_lib], or None"""
+    if role is not None and (case is not None or control is not None):
+        raise ValueError("give role, or case / control, not both")
+    if role is None and case is None and control is None:
+        return None
+    if role is not None:
+        r = np.asarray(role).ravel()
+        if r.size != n_lib or (r.astype(np.int64) != r).any() or ((r < 0) | (r > capi.ROLE_CONTROL)).any():
+            raise ValueError("role: one of 0 (ignore), 1 (case), 2 (control) per library, %d of them" % n_lib)
+        r = r.astype(np.uint8)
+    else:
+        names = [b.decode() for b in engine._names]
+        if len(names) != n_lib:
+            raise ValueError("case / control name libraries: the engine reports one set of counts for all of them")
+        r = np.zeros(n_lib, np.uint8)
+        for value, given in ((capi.ROLE_CASE, case), (capi.ROLE_CONTROL, control)):
+            for name in ([given] if isinstance(given, (str, bytes)) else list(given or [])):
+                name = name.decode() if isinstance(name, bytes) else name
+                if name not in names:
+                    raise ValueError("%r is not a library of the engine (%r)" % (name, names))
+                if r[names.index(name)]:
+                    raise ValueError("library %r is named twice" % name)
+                r[names.index(name)] = value
+    if not (r == capi.ROLE_CASE).any():
+        raise ValueError("no case library")
+    return r
+
+
+def _u32(x, what):
+    if isinstance(x, bool) or int(x) != x or not 0 <= int(x) < 2 ** 32:
+        raise ValueError("%s must be an integer in [0, 2^32)" % what)
+    return int(x)
+
+
+def select(engine, select, *, role=None, case=None, control=None, snv=True, indel=True, min_depth, min_alt, min_frac=(0, 1), ctl_min_depth=0,
+           ctl_max_alt=2 ** 32 - 1, ctl_max_frac=(1, 1), beg0=None, end=None):
+    """The positions of [beg0, end) of the engine's last computed region (clipped as region() clips) that carry non-reference evidence
+    in a case library and none in the control libraries — include/brc_select.h has the exact integer predicate:
+      a base b other than the reference's (snv) or an insertion / a deletion (indel) with, in SOME case library, depth >= min_depth,
+      count >= min_alt and count / depth >= min_frac (num, den), and in EVERY control library depth >= ctl_min_depth, count <=
+      ctl_max_alt and count / depth <= ctl_max_frac.  Allele text is not compared: a control insertion of any spelling counts against an
+      insertion candidate.
+    role: one of capi.ROLE_IGNORE / ROLE_CASE / ROLE_CONTROL per library; or case= / control= lists of the engine's library names (the
+    others are ignored); none of them: every library is a case library.
+
+    Returns {"idx": int32 [n] plane indices, ascending, "pos": int32 [n] = pos0 + idx, "why": int32 [n] the reason bits (capi.WHY_*),
+    "n": int, "first": int, "pos0": int}.  With the HIP libraries the arrays are torch tensors on the engine's device, filled on
+    torch's current stream, the scratch comes from torch.empty; with the CPU builds they are numpy arrays.  "pos" is what
+    sites(positions=...) takes.
+
+    SYNCHRONISES ONCE: the list's length is data.  A first call asks for the count alone, the host reads it (as torch.nonzero does),
+    then the list is allocated exactly and a second call fills it without another wait.
+    ValueError for parameters the library would refuse, before anything is queued."""
+    flags = (capi.SELECT_SNV if snv else 0) | (capi.SELECT_INDEL if indel else 0)
+    if not flags:
+        raise ValueError("nothing to look for: snv and indel are both off")
+    for pair, what in ((min_frac, "min_frac"), (ctl_max_frac, "ctl_max_frac")):
+        if len(pair) != 2:
+            raise ValueError("%s is a pair (numerator, denominator)" % what)
+    frac = (_u32(min_frac[0], "min_frac"), _u32(min_frac[1], "min_frac"))
+    cfrac = (_u32(ctl_max_frac[0], "ctl_max_frac"), _u32(ctl_max_frac[1], "ctl_max_frac"))
+    if frac[1] == 0 or cfrac[1] == 0:
+        raise ValueError("a fraction's denominator must not be 0")
+    if _u32(min_alt, "min_alt") == 0:
+        raise ValueError("min_alt must be at least 1")
+    v, d = engine.device_view(), engine.device_indels()
+    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    if L > capi.SELECT_MAX_LIB:
+        raise ValueError("the selector takes at most %d libraries" % capi.SELECT_MAX_LIB)
+    roles = _roles(engine, L, role, case, control)
+    params, keep = capi.select_params(roles, flags, _u32(min_depth, "min_depth"), int(min_alt), frac, _u32(ctl_min_depth, "ctl_min_depth"),
+                                      _u32(ctl_max_alt, "ctl_max_alt"), cfrac)
+    lo = pos0 if beg0 is None else max(int(beg0), pos0)
+    hi = pos0 + P if end is None else min(int(end), pos0 + P)
+    lo = min(lo, pos0 + P)
+    n = max(hi - lo, 0)
+    k0 = lo - pos0 if n else 0
+    wsb = select.workspace(v, d, n)
+    if v.memory == capi.MEM_HOST:
+        def empty(m):
+            return np.empty(m, np.int32)
+        ptr, stream = (lambda a: a.ctypes.data), None
+        counts = np.zeros(1, np.int32)
+    elif v.memory == capi.MEM_DEVICE:
+        import torch          # (lazily: the package and its CPU route work without torch)
+        dev = torch.device("cuda", int(v.device))
+
+        def empty(m):
+            return torch.empty(m, dtype=torch.int32, device=dev)
+        ptr = lambda a: a.data_ptr()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+        counts = torch.zeros(1, dtype=torch.int32, device=dev)
+    else:
+        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
+    ws = empty(max(wsb // 4, 1))
+    select.sites(v, d, params, k0, n, counts=ptr(counts), workspace=ptr(ws), stream=stream)
+    m = int(counts[0]) & 0xFFFFFFFF                                       # the one wait
+    idx, why = empty(m), empty(m)
+    if m:
+        select.sites(v, d, params, k0, n, cap=m, idx=ptr(idx), why=ptr(why), workspace=ptr(ws), stream=stream)
+    del keep
+    return {"idx": idx, "pos": idx + np.int32(pos0) if v.memory == capi.MEM_HOST else idx + pos0, "why": why, "n": m, "first": pos0 + k0, "pos0": pos0}
