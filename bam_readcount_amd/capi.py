@@ -1045,3 +1045,91 @@ class Select:
         k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
         self.lib.brc_select_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
         return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+
+
+# ---------------------------------------------------------------- device-side window summaries (include/brc_bins.h)
+BINS_LIB = os.path.join(HERE, "csrc", "libbrc_bins_hip.so")
+BINS_EXPORTS = [
+    "brc_bins_create", "brc_bins_destroy", "brc_bins_kind", "brc_bins_last_error", "brc_bins_reduce", "brc_bins_last_timing",
+]
+BINS_NSUM, BINS_MAX_THR, BINS_MAX_HIST, BINS_MAX_LIB = 12, 8, 4096, 65535
+BINS_S_DEPTH, BINS_S_NCOL, BINS_S_BUCKET, BINS_S_NONREF, BINS_S_INS, BINS_S_DEL, BINS_S_MAXDEPTH = 0, 1, 2, 8, 9, 10, 11
+BINS_DESCENDS, BINS_OUTSIDE = 1, 2
+
+
+class BinsParams(C.Structure):
+    """brc_bins_params (include/brc_bins.h)"""
+    _fields_ = [("edges", C.c_void_p), ("width", C.c_int64), ("n_bins", C.c_int64), ("n_thr", C.c_int32), ("n_hist", C.c_int32),
+                ("thr", C.c_uint32 * BINS_MAX_THR)]
+
+
+def bins_params(width=0, edges=None, n_bins=0, thresholds=(), n_hist=0):
+    """BinsParams: uniform bins of `width` positions, or an edge list — the ADDRESS of n_bins + 1 int32 plane indices in the views' kind
+    of memory (the caller keeps them alive)"""
+    p = BinsParams(edges, width, n_bins, len(thresholds), n_hist)
+    for t, x in enumerate(thresholds[:BINS_MAX_THR]):
+        p.thr[t] = x
+    return p
+
+
+class Bins:
+    """One handle of a library exporting include/brc_bins.h: the product's libbrc_bins_hip.so (default; raises when it is not built or
+    there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_bins).  reduce() takes raw
+    addresses; bam_readcount_amd.tensors.bins() is the interface that allocates and returns arrays."""
+
+    def __init__(self, path=None, device=0):
+        path = path or BINS_LIB
+        if not os.path.exists(path):
+            raise BrcError("bins library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
+        self.path = path
+        self.lib = L = _load(path)
+        for s in BINS_EXPORTS:
+            if not hasattr(L, s):
+                raise BrcError("%s does not export %s" % (path, s))
+        L.brc_bins_kind.restype = C.c_char_p
+        L.brc_bins_last_error.restype = C.c_char_p; L.brc_bins_last_error.argtypes = [C.c_void_p]
+        L.brc_bins_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+        L.brc_bins_destroy.argtypes = [C.c_void_p]; L.brc_bins_destroy.restype = None
+        L.brc_bins_reduce.argtypes = ([C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(BinsParams), C.c_int64, C.c_int64] +
+                                      [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p])
+        L.brc_bins_last_timing.restype = None
+        L.brc_bins_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        self.device = device
+        h = C.c_void_p()
+        rc = L.brc_bins_create(device, C.byref(h))
+        if rc != 0:
+            e = BrcError("brc_bins_create failed: %d" % rc)
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def kind(self):
+        return self.lib.brc_bins_kind().decode()
+
+    def close(self):
+        if self.h:
+            self.lib.brc_bins_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reduce_raw(self, view, indels, params, k0, n, dst_stride, sums=None, covered=None, hist=None, status=None, stream=None):
+        """brc_bins_reduce as it is: destinations and the status word are addresses (or None) in memory of the views' kind; returns the
+        code."""
+        return self.lib.brc_bins_reduce(self.h, C.byref(view) if view is not None else None, C.byref(indels) if indels is not None else None,
+                                        C.byref(params) if params is not None else None, k0, n, sums, covered, hist, dst_stride, status, stream)
+
+    def reduce(self, view, indels, params, k0, n, dst_stride, **kw):
+        rc = self.reduce_raw(view, indels, params, k0, n, dst_stride, **kw)
+        if rc != 0:
+            raise BrcError("brc_bins_reduce: %d (%s)" % (rc, self.lib.brc_bins_last_error(self.h).decode()))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last reduction), bytes asked for and destination bytes cleared"""
+        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
+        self.lib.brc_bins_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
+        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)

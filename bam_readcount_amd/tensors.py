@@ -25,6 +25,10 @@ The positions worth listing can be picked on the device too: select() returns th
 a deletion) in "case" libraries and none in "control" libraries, found by libbrc_select_hip.so (capi.Select) over the compact planes:
     sel = tensors.select(eng, select, case=["tumor"], control=["normal"], min_depth=10, min_alt=3, min_frac=(1, 20), ctl_max_alt=0)
     panel = tensors.sites(eng, capi.Panel(), positions=sel["pos"])
+
+Per-window questions — depth, coverage at thresholds, allele and indel load per bin and library, a depth histogram — are answered by
+bins(): exact integer sums over uniform bins or an edge list, reduced by libbrc_bins_hip.so (capi.Bins) without a synchronisation:
+    cov = tensors.bins(eng, capi.Bins(), width=1000, thresholds=(10, 20, 30), hist=256)
 """
 import numpy as np
 
@@ -417,3 +421,110 @@ def select(engine, select, *, role=None, case=None, control=None, snv=True, inde
         select.sites(v, d, params, k0, n, cap=m, idx=ptr(idx), why=ptr(why), workspace=ptr(ws), stream=stream)
     del keep
     return {"idx": idx, "pos": idx + np.int32(pos0) if v.memory == capi.MEM_HOST else idx + pos0, "why": why, "n": m, "first": pos0 + k0, "pos0": pos0}
+
+
+BIN_KINDS = ("sums", "covered", "hist")
+
+
+def bins(engine, bins, *, width=None, edges=None, thresholds=(), hist=0, beg0=None, end=None, want=BIN_KINDS):
+    """Per-bin summaries of the reference positions [beg0, end) of the engine's last computed region (clipped as region() clips),
+    reduced where the region lies by libbrc_bins_hip.so (capi.Bins) — include/brc_bins.h has the exact definitions.
+
+    Exactly one of
+      width: uniform bins of `width` positions from the window's first position on (the last one may be shorter);
+      edges: n_bins + 1 reference (axis) positions; bin b is [edges[b], edges[b + 1]), positions outside [edges[0], edges[-1]) lie in no
+             bin, equal neighbours make an empty bin.  A sequence or numpy array is checked on the host — non-descending and inside the
+             window [first, first + n], ValueError otherwise, before anything is queued — and uploaded once.  A one-dimensional int32
+             torch tensor on the engine's device (HIP libraries) is used where it lies and NOT checked; nothing synchronises: "status"
+             tells afterwards (capi.BINS_DESCENDS: the bins are what a binary search finds; capi.BINS_OUTSIDE: such edges count as
+             the window's ends).
+    thresholds: up to capi.BINS_MAX_THR depths for "covered"; hist: the bars of the depth histogram (0: none; depths of hist - 1 and
+    above share the last bar).
+
+    Returns a dict: every kind in `want` (BIN_KINDS) ->
+      "sums"    uint64 [n_lib, capi.BINS_NSUM, n_bins]: per library and bin the sums of depth, ncol, the reads of the six buckets
+                "=ACGTN", the non-reference reads, the insertion reads, the deletion reads, and the largest depth (capi.BINS_S_*)
+      "covered" uint64 [n_lib, len(thresholds), n_bins]: positions with depth >= thresholds[t]
+      "hist"    uint64 [n_lib, hist]: positions that lie in some bin, by min(depth, hist - 1)
+    plus "status" (one uint32 element in the arrays' memory, written by the kernels, not read by this call), for uniform bins "start"
+    (int64 [n_bins]: the reference position each bin starts at) and the ints "n_bins", "first", "n", "n_lib", "pos0".  Integer sums
+    only: a mean is sums / (edges' differences or width), the caller's division (torch: .view(torch.int64) first — torch has few
+    operators on unsigned types).
+    With the HIP libraries the arrays are torch tensors on the engine's device, filled on torch's current stream; every size is
+    known on the host, so NOTHING SYNCHRONISES.  With the CPU builds they are numpy arrays."""
+    want = tuple(want)
+    for k in want:
+        if k not in BIN_KINDS:
+            raise ValueError("unknown kind %r (one of %r)" % (k, BIN_KINDS))
+    if (width is None) == (edges is None):
+        raise ValueError("give exactly one of width and edges")
+    thr = [_u32(t, "a threshold") for t in thresholds]
+    if len(thr) > capi.BINS_MAX_THR:
+        raise ValueError("at most %d thresholds" % capi.BINS_MAX_THR)
+    if isinstance(hist, bool) or int(hist) != hist or not 0 <= int(hist) <= capi.BINS_MAX_HIST:
+        raise ValueError("hist: 0 .. %d bars" % capi.BINS_MAX_HIST)
+    n_hist = int(hist)
+    if width is not None and (isinstance(width, bool) or int(width) != width or int(width) < 1):
+        raise ValueError("width must be a positive integer")
+    v, d = engine.device_view(), engine.device_indels()
+    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    if v.memory not in (capi.MEM_HOST, capi.MEM_DEVICE):
+        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
+    lo = pos0 if beg0 is None else max(int(beg0), pos0)
+    hi = pos0 + P if end is None else min(int(end), pos0 + P)
+    lo = min(lo, pos0 + P)
+    n = max(hi - lo, 0)
+    k0 = lo - pos0 if n else 0
+    first = pos0 + k0
+    on_device = edges is not None and type(edges).__module__.split(".")[0] == "torch"
+    host_edges = None
+    if width is not None:
+        n_bins = (n + int(width) - 1) // int(width)
+    elif on_device:
+        if v.memory != capi.MEM_DEVICE:
+            raise ValueError("a torch tensor of edges needs an engine whose results lie on a GPU")
+        n_bins = int(edges.numel()) - 1
+    else:
+        e = np.asarray(edges)
+        if e.ndim != 1 or e.size < 1 or (e.size and (e.astype(np.int64) != e).any()):
+            raise ValueError("edges: a one-dimensional list of at least one integer position")
+        e = e.astype(np.int64)
+        if (e[1:] < e[:-1]).any():
+            raise ValueError("the edges must not descend")
+        if e[0] < first or e[-1] > first + n:
+            raise ValueError("edges outside the window [%d, %d]" % (first, first + n))
+        host_edges = (e - pos0).astype(np.int32)
+        n_bins = int(e.size) - 1
+    if n_bins < 0:
+        raise ValueError("edges: at least one position")
+    shp = {"sums": (L, capi.BINS_NSUM, n_bins), "covered": (L, len(thr), n_bins), "hist": (L, n_hist)}
+    if v.memory == capi.MEM_HOST:
+        arrays = {k: np.empty(shp[k], np.uint64) for k in want}
+        ptr, stream = (lambda a: a.ctypes.data if a.size else None), None
+        status = np.zeros(1, np.uint32)
+        idx = host_edges
+        start = first + np.arange(n_bins, dtype=np.int64) * int(width) if width is not None else None
+    else:
+        import torch          # (lazily: the package and its CPU route work without torch)
+        dev = torch.device("cuda", int(v.device))
+        arrays = {k: torch.empty(shp[k], dtype=torch.int64, device=dev).view(torch.uint64) for k in want}
+        ptr = lambda a: a.data_ptr() if a.numel() else None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+        status = torch.zeros(1, dtype=torch.int32, device=dev).view(torch.uint32)
+        if on_device:
+            if edges.dtype != torch.int32 or edges.device != dev or edges.dim() != 1 or not edges.is_contiguous():
+                raise ValueError("edges must be a contiguous one-dimensional int32 tensor on %s" % dev)
+            idx = edges - pos0
+        else:
+            idx = torch.from_numpy(host_edges).to(dev) if host_edges is not None else None
+        start = first + torch.arange(n_bins, dtype=torch.int64, device=dev) * int(width) if width is not None else None
+    params = capi.bins_params(int(width) if width is not None else 0, ptr(idx) if idx is not None else None, n_bins if width is None else 0, thr, n_hist)
+    if width is None and params.edges is None:
+        raise ValueError("edges: at least one position")
+    bins.reduce(v, d, params, k0, n, n_bins, status=ptr(status), stream=stream, **{k: ptr(arrays[k]) for k in want})
+    res = {"n_bins": n_bins, "first": first, "n": n, "n_lib": L, "pos0": pos0, "status": status}
+    if start is not None:
+        res["start"] = start
+    res.update(arrays)
+    return res
