@@ -553,6 +553,79 @@ def kernel_object_hash(path=None):
     return None
 
 
+class _Handle:
+    """What the handle classes below share: one handle of one loaded library whose C-ABI names start with PREFIX.  The base checks the
+    path and the exports, declares the prototypes, creates the handle (a refusal is a BrcError carrying the code as .rc) and owns
+    kind(), close(), the (kernel_s, bytes_read, bytes_written) last_timing() and the rc -> BrcError(last_error) check.  A subclass sets
+      PREFIX    "brc_dense": the handle's calls are brc_dense_create, _destroy, _kind, _last_error, _last_timing
+      EXPORTS   every symbol the library must export
+      LIB       the product's library, loaded when no path is given
+      NAME      what the "not found" message calls the library
+      PROTOS    {symbol: (restype, argtypes)} of the calls that are the library's own
+      TIMING    the argtypes of _last_timing behind the handle, where they are not the three of the side libraries
+    and holds its own methods only."""
+    TIMING = [C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    PROTOS = {}
+
+    def __init__(self, path=None, device=0):
+        path = path or self.LIB
+        if not os.path.exists(path):
+            raise BrcError("%s library not found: %s (run `python __graft_entry__.py` / build() first)" % (self.NAME, path))
+        self.path = path
+        self.lib = L = _load(path)
+        for s in self.EXPORTS:
+            if not hasattr(L, s):
+                raise BrcError("%s does not export %s" % (path, s))
+        protos = {"_kind": (C.c_char_p, []), "_last_error": (C.c_char_p, [C.c_void_p]), "_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+                  "_destroy": (None, [C.c_void_p]), "_last_timing": (None, [C.c_void_p] + self.TIMING)}
+        protos = {self.PREFIX + k: v for k, v in protos.items()}
+        protos.update(self.PROTOS)
+        for name, (restype, argtypes) in protos.items():
+            f = getattr(L, name)
+            f.restype = restype; f.argtypes = argtypes
+        self.device = device
+        h = C.c_void_p()
+        rc = self._call("_create")(device, C.byref(h))
+        if rc != 0:
+            e = BrcError("%s_create failed: %d" % (self.PREFIX, rc))
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def _call(self, suffix):
+        return getattr(self.lib, self.PREFIX + suffix)
+
+    def kind(self):
+        return self._call("_kind")().decode()
+
+    def close(self):
+        if self.h:
+            self._call("_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, call, rc):
+        if rc != 0:
+            raise BrcError("%s: %d (%s)" % (call, rc, self._call("_last_error")(self.h).decode()))
+
+    def last_timing(self):
+        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
+        self._call("_last_timing")(self.h, C.byref(k), C.byref(r), C.byref(w))
+        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+
+
+def _ref(x):
+    return C.byref(x) if x is not None else None
+
+
+_TIMING5 = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+
+
 # ---------------------------------------------------------------- the BGZF inflater (include/brc_inflate.h)
 INFLATE_LIB = os.path.join(HERE, "csrc", "libbrc_inflate_hip.so")
 INFLATE_EXPORTS = [
@@ -563,44 +636,13 @@ INF_OK, INF_BAD_HEADER, INF_BAD_STREAM, INF_SIZE_MISMATCH, INF_CRC_MISMATCH, INF
 E_ARG, E_NODEVICE = -1, -2
 
 
-class Inflater:
+class Inflater(_Handle):
     """One inflater handle of a library exporting include/brc_inflate.h: the product's libbrc_inflate_hip.so (default; raises when it
     is not built or there is no device — nothing falls back) or the CPU build of the same decoder (tests/sim_inflate)."""
 
-    def __init__(self, path=None, device=0):
-        path = path or INFLATE_LIB
-        if not os.path.exists(path):
-            raise BrcError("inflater library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
-        self.path = path
-        self.lib = L = _load(path)
-        L.brc_inflater_kind.restype = C.c_char_p
-        L.brc_inflater_last_error.restype = C.c_char_p; L.brc_inflater_last_error.argtypes = [C.c_void_p]
-        L.brc_inflater_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.brc_inflater_destroy.argtypes = [C.c_void_p]; L.brc_inflater_destroy.restype = None
-        L.brc_inflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
-        L.brc_inflate_host_alloc.restype = C.c_void_p; L.brc_inflate_host_alloc.argtypes = [C.c_size_t]
-        L.brc_inflate_host_free.restype = None; L.brc_inflate_host_free.argtypes = [C.c_void_p]
-        L.brc_inflater_last_timing.restype = None
-        L.brc_inflater_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        h = C.c_void_p()
-        rc = L.brc_inflater_create(device, C.byref(h))
-        if rc != 0:
-            raise BrcError("brc_inflater_create failed: %d" % rc)
-        self.h = h
-
-    def kind(self):
-        return self.lib.brc_inflater_kind().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.brc_inflater_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, EXPORTS, LIB, NAME, TIMING = "brc_inflater", INFLATE_EXPORTS, INFLATE_LIB, "inflater", _TIMING5
+    PROTOS = {"brc_inflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+              "brc_inflate_host_alloc": (C.c_void_p, [C.c_size_t]), "brc_inflate_host_free": (None, [C.c_void_p])}
 
     def inflate_raw(self, src, dst_cap=None, capacity=None, whole=False):
         """brc_inflate_bgzf as it is: (rc, bytes of dst, dst_off[0..n], statuses[0..n)).  dst_cap / capacity None: sized by a first,
@@ -626,8 +668,7 @@ class Inflater:
         """Raw BGZF bytes (whole members back to back) -> (inflated bytes, offsets (n + 1), statuses (n)).  Raises when src is not a
         chain of whole members; members that failed are reported by their status, their bytes are not meaningful."""
         rc, out, off, st, _ = self.inflate_raw(src)
-        if rc != 0:
-            raise BrcError("brc_inflate_bgzf: %d (%s)" % (rc, self.lib.brc_inflater_last_error(self.h).decode()))
+        self._check("brc_inflate_bgzf", rc)
         return out, off, st
 
     def last_timing(self):
@@ -645,52 +686,15 @@ DEFLATE_EXPORTS = [
 DEFLATE_MEMBER_INPUT = 0xff00
 
 
-def _bind_deflate(L):
-    L.brc_deflater_kind.restype = C.c_char_p
-    L.brc_deflater_last_error.restype = C.c_char_p; L.brc_deflater_last_error.argtypes = [C.c_void_p]
-    L.brc_deflater_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-    L.brc_deflater_destroy.argtypes = [C.c_void_p]; L.brc_deflater_destroy.restype = None
-    L.brc_deflate_bound.restype = C.c_size_t; L.brc_deflate_bound.argtypes = [C.c_size_t]
-    L.brc_deflate_bgzf.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.brc_deflate_eof_block.restype = C.c_void_p; L.brc_deflate_eof_block.argtypes = [C.POINTER(C.c_size_t)]
-    L.brc_deflate_host_alloc.restype = C.c_void_p; L.brc_deflate_host_alloc.argtypes = [C.c_size_t]
-    L.brc_deflate_host_free.restype = None; L.brc_deflate_host_free.argtypes = [C.c_void_p]
-    L.brc_deflater_last_timing.restype = None
-    L.brc_deflater_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    return L
-
-
-class Deflater:
+class Deflater(_Handle):
     """One deflater handle of a library exporting include/brc_deflate.h: the product's libbrc_deflate_hip.so (default; raises when it
     is not built or there is no device — nothing falls back) or the CPU build of the same compressor (tests/sim_deflate)."""
 
-    def __init__(self, path=None, device=0):
-        path = path or DEFLATE_LIB
-        if not os.path.exists(path):
-            raise BrcError("deflater library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
-        self.path = path
-        self.lib = L = _bind_deflate(_load(path))
-        h = C.c_void_p()
-        rc = L.brc_deflater_create(device, C.byref(h))
-        if rc != 0:
-            e = BrcError("brc_deflater_create failed: %d" % rc)
-            e.rc = rc
-            raise e
-        self.h = h
-
-    def kind(self):
-        return self.lib.brc_deflater_kind().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.brc_deflater_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, EXPORTS, LIB, NAME, TIMING = "brc_deflater", DEFLATE_EXPORTS, DEFLATE_LIB, "deflater", _TIMING5
+    PROTOS = {"brc_deflate_bound": (C.c_size_t, [C.c_size_t]),
+              "brc_deflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+              "brc_deflate_eof_block": (C.c_void_p, [C.POINTER(C.c_size_t)]),
+              "brc_deflate_host_alloc": (C.c_void_p, [C.c_size_t]), "brc_deflate_host_free": (None, [C.c_void_p])}
 
     def bound(self, n):
         return int(self.lib.brc_deflate_bound(n))
@@ -719,8 +723,7 @@ class Deflater:
     def deflate(self, src):
         """Any bytes -> whole BGZF members back to back (no end-of-file member)."""
         rc, out, _ = self.deflate_raw(src)
-        if rc != 0:
-            raise BrcError("brc_deflate_bgzf: %d (%s)" % (rc, self.lib.brc_deflater_last_error(self.h).decode()))
+        self._check("brc_deflate_bgzf", rc)
         return out
 
     def last_timing(self):
@@ -739,65 +742,24 @@ M_NAMES = ["count", "avg_mapq", "avg_bq", "avg_se_mapq", "plus", "minus", "avg_p
            "avg_clipped", "avg_3p"]
 
 
-class Dense:
+class Dense(_Handle):
     """One handle of a library exporting include/brc_dense.h: the product's libbrc_dense_hip.so (default; raises when it is not built
     or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_dense).  expand() takes
     raw addresses; bam_readcount_amd.tensors.region() is the interface that allocates and returns arrays."""
 
-    def __init__(self, path=None, device=0):
-        path = path or DENSE_LIB
-        if not os.path.exists(path):
-            raise BrcError("dense library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
-        self.path = path
-        self.lib = L = _load(path)
-        for s in DENSE_EXPORTS:
-            if not hasattr(L, s):
-                raise BrcError("%s does not export %s" % (path, s))
-        L.brc_dense_kind.restype = C.c_char_p
-        L.brc_dense_last_error.restype = C.c_char_p; L.brc_dense_last_error.argtypes = [C.c_void_p]
-        L.brc_dense_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.brc_dense_destroy.argtypes = [C.c_void_p]; L.brc_dense_destroy.restype = None
-        L.brc_dense_expand.argtypes = [C.c_void_p, C.POINTER(DeviceView), C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7
-        L.brc_dense_last_timing.restype = None
-        L.brc_dense_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        self.device = device
-        h = C.c_void_p()
-        rc = L.brc_dense_create(device, C.byref(h))
-        if rc != 0:
-            e = BrcError("brc_dense_create failed: %d" % rc)
-            e.rc = rc
-            raise e
-        self.h = h
-
-    def kind(self):
-        return self.lib.brc_dense_kind().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.brc_dense_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, EXPORTS, LIB, NAME = "brc_dense", DENSE_EXPORTS, DENSE_LIB, "dense"
+    PROTOS = {"brc_dense_expand": (C.c_int, [C.c_void_p, C.POINTER(DeviceView), C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7)}
 
     def expand_raw(self, view, k0, n, dst_stride, ncol=None, depth=None, unavail=None, istat=None, fstat=None, metrics=None, stream=None):
         """brc_dense_expand as it is: destinations are addresses (or None) in memory of the view's kind; returns the code."""
-        return self.lib.brc_dense_expand(self.h, C.byref(view) if view is not None else None, k0, n, dst_stride,
-                                         ncol, depth, unavail, istat, fstat, metrics, stream)
+        return self.lib.brc_dense_expand(self.h, _ref(view), k0, n, dst_stride, ncol, depth, unavail, istat, fstat, metrics, stream)
 
     def expand(self, view, k0, n, dst_stride, **kw):
-        rc = self.expand_raw(view, k0, n, dst_stride, **kw)
-        if rc != 0:
-            raise BrcError("brc_dense_expand: %d (%s)" % (rc, self.lib.brc_dense_last_error(self.h).decode()))
+        self._check("brc_dense_expand", self.expand_raw(view, k0, n, dst_stride, **kw))
 
     def last_timing(self):
         """kernel seconds (waits for the launches of the last expand), bytes read and written"""
-        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
-        self.lib.brc_dense_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
-        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+        return super().last_timing()
 
 
 # ---------------------------------------------------------------- the device-resident indel table (include/brc_indels.h)
@@ -809,72 +771,32 @@ INDELS_EXPORTS = [
 INDEL_DESTS = ("pos", "lib", "len", "rep_read", "rep_qpos", "istat", "fstat", "metrics", "allele_off", "alleles")
 
 
-class Indels:
+class Indels(_Handle):
     """One handle of a library exporting include/brc_indels.h: the product's libbrc_indels_hip.so (default; raises when it is not built
     or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_indels).  gather() takes
     raw addresses; bam_readcount_amd.tensors.indels() is the interface that allocates and returns arrays."""
 
-    def __init__(self, path=None, device=0):
-        path = path or INDELS_LIB
-        if not os.path.exists(path):
-            raise BrcError("indels library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
-        self.path = path
-        self.lib = L = _load(path)
-        for s in INDELS_EXPORTS:
-            if not hasattr(L, s):
-                raise BrcError("%s does not export %s" % (path, s))
-        L.brc_indels_kind.restype = C.c_char_p
-        L.brc_indels_last_error.restype = C.c_char_p; L.brc_indels_last_error.argtypes = [C.c_void_p]
-        L.brc_indels_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.brc_indels_destroy.argtypes = [C.c_void_p]; L.brc_indels_destroy.restype = None
-        L.brc_indels_workspace.restype = C.c_size_t; L.brc_indels_workspace.argtypes = [C.POINTER(DeviceIndels), C.c_int64]
-        L.brc_indels_gather.argtypes = ([C.c_void_p, C.POINTER(DeviceIndels), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int64] +
-                                        [C.c_void_p] * 11)
-        L.brc_indels_last_timing.restype = None
-        L.brc_indels_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        self.device = device
-        h = C.c_void_p()
-        rc = L.brc_indels_create(device, C.byref(h))
-        if rc != 0:
-            e = BrcError("brc_indels_create failed: %d" % rc)
-            e.rc = rc
-            raise e
-        self.h = h
-
-    def kind(self):
-        return self.lib.brc_indels_kind().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.brc_indels_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, EXPORTS, LIB, NAME = "brc_indels", INDELS_EXPORTS, INDELS_LIB, "indels"
+    PROTOS = {"brc_indels_workspace": (C.c_size_t, [C.POINTER(DeviceIndels), C.c_int64]),
+              "brc_indels_gather": (C.c_int, [C.c_void_p, C.POINTER(DeviceIndels), C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.c_int64] +
+                                    [C.c_void_p] * 11)}
 
     def workspace(self, view, n):
         """bytes of scratch a gather over n positions of the view needs"""
-        return int(self.lib.brc_indels_workspace(C.byref(view) if view is not None else None, n))
+        return int(self.lib.brc_indels_workspace(_ref(view), n))
 
     def gather_raw(self, view, k0, n, workspace=None, workspace_bytes=0, counts=None, cap=0, alleles_cap=0, pos=None, lib=None, len=None,
                    rep_read=None, rep_qpos=None, istat=None, fstat=None, metrics=None, allele_off=None, alleles=None, stream=None):
         """brc_indels_gather as it is: scratch and destinations are addresses (or None) in memory of the view's kind; returns the code."""
-        return self.lib.brc_indels_gather(self.h, C.byref(view) if view is not None else None, k0, n, workspace, workspace_bytes, counts,
+        return self.lib.brc_indels_gather(self.h, _ref(view), k0, n, workspace, workspace_bytes, counts,
                                           cap, alleles_cap, pos, lib, len, rep_read, rep_qpos, istat, fstat, metrics, allele_off, alleles, stream)
 
     def gather(self, view, k0, n, **kw):
-        rc = self.gather_raw(view, k0, n, **kw)
-        if rc != 0:
-            raise BrcError("brc_indels_gather: %d (%s)" % (rc, self.lib.brc_indels_last_error(self.h).decode()))
+        self._check("brc_indels_gather", self.gather_raw(view, k0, n, **kw))
 
     def last_timing(self):
         """kernel seconds (waits for the launches of the last gather), bytes read and written"""
-        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
-        self.lib.brc_indels_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
-        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+        return super().last_timing()
 
 
 # ---------------------------------------------------------------- device-resident site panels (include/brc_panel.h)
@@ -886,67 +808,27 @@ PANEL_OUT_OF_RANGE, PANEL_NOT_ASCENDING = 1, 2
 PANEL_DESTS = ("ncol", "depth", "unavail", "istat", "fstat", "metrics")
 
 
-class Panel:
+class Panel(_Handle):
     """One handle of a library exporting include/brc_panel.h: the product's libbrc_panel_hip.so (default; raises when it is not built
     or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_panel).  gather() takes
     raw addresses; bam_readcount_amd.tensors.sites() is the interface that allocates and returns arrays."""
 
-    def __init__(self, path=None, device=0):
-        path = path or PANEL_LIB
-        if not os.path.exists(path):
-            raise BrcError("panel library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
-        self.path = path
-        self.lib = L = _load(path)
-        for s in PANEL_EXPORTS:
-            if not hasattr(L, s):
-                raise BrcError("%s does not export %s" % (path, s))
-        L.brc_panel_kind.restype = C.c_char_p
-        L.brc_panel_last_error.restype = C.c_char_p; L.brc_panel_last_error.argtypes = [C.c_void_p]
-        L.brc_panel_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.brc_panel_destroy.argtypes = [C.c_void_p]; L.brc_panel_destroy.restype = None
-        L.brc_panel_gather.argtypes = [C.c_void_p, C.POINTER(DeviceView), C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8
-        L.brc_panel_last_timing.restype = None
-        L.brc_panel_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        self.device = device
-        h = C.c_void_p()
-        rc = L.brc_panel_create(device, C.byref(h))
-        if rc != 0:
-            e = BrcError("brc_panel_create failed: %d" % rc)
-            e.rc = rc
-            raise e
-        self.h = h
-
-    def kind(self):
-        return self.lib.brc_panel_kind().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.brc_panel_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, EXPORTS, LIB, NAME = "brc_panel", PANEL_EXPORTS, PANEL_LIB, "panel"
+    PROTOS = {"brc_panel_gather": (C.c_int, [C.c_void_p, C.POINTER(DeviceView), C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 8)}
 
     def gather_raw(self, view, idx, n, dst_stride, ncol=None, depth=None, unavail=None, istat=None, fstat=None, metrics=None, status=None,
                    stream=None):
         """brc_panel_gather as it is: the list, the destinations and the status word are addresses (or None) in memory of the view's
         kind; returns the code."""
-        return self.lib.brc_panel_gather(self.h, C.byref(view) if view is not None else None, idx, n, dst_stride,
+        return self.lib.brc_panel_gather(self.h, _ref(view), idx, n, dst_stride,
                                          ncol, depth, unavail, istat, fstat, metrics, status, stream)
 
     def gather(self, view, idx, n, dst_stride, **kw):
-        rc = self.gather_raw(view, idx, n, dst_stride, **kw)
-        if rc != 0:
-            raise BrcError("brc_panel_gather: %d (%s)" % (rc, self.lib.brc_panel_last_error(self.h).decode()))
+        self._check("brc_panel_gather", self.gather_raw(view, idx, n, dst_stride, **kw))
 
     def last_timing(self):
         """kernel seconds (waits for the launches of the last gather), bytes asked for and written"""
-        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
-        self.lib.brc_panel_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
-        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+        return super().last_timing()
 
 
 # ---------------------------------------------------------------- device-side site selection (include/brc_select.h)
@@ -979,72 +861,30 @@ def select_params(role=None, flags=SELECT_SNV | SELECT_INDEL, min_depth=0, min_a
     return p, keep
 
 
-class Select:
+class Select(_Handle):
     """One handle of a library exporting include/brc_select.h: the product's libbrc_select_hip.so (default; raises when it is not built
     or there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_select).  sites() takes
     raw addresses; bam_readcount_amd.tensors.select() is the interface that allocates and returns arrays."""
 
-    def __init__(self, path=None, device=0):
-        path = path or SELECT_LIB
-        if not os.path.exists(path):
-            raise BrcError("select library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
-        self.path = path
-        self.lib = L = _load(path)
-        for s in SELECT_EXPORTS:
-            if not hasattr(L, s):
-                raise BrcError("%s does not export %s" % (path, s))
-        L.brc_select_kind.restype = C.c_char_p
-        L.brc_select_last_error.restype = C.c_char_p; L.brc_select_last_error.argtypes = [C.c_void_p]
-        L.brc_select_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.brc_select_destroy.argtypes = [C.c_void_p]; L.brc_select_destroy.restype = None
-        L.brc_select_workspace.restype = C.c_int64
-        L.brc_select_workspace.argtypes = [C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.c_int64]
-        L.brc_select_sites.argtypes = ([C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(SelectParams), C.c_int64, C.c_int64, C.c_int64] +
-                                       [C.c_void_p] * 5)
-        L.brc_select_last_timing.restype = None
-        L.brc_select_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        self.device = device
-        h = C.c_void_p()
-        rc = L.brc_select_create(device, C.byref(h))
-        if rc != 0:
-            e = BrcError("brc_select_create failed: %d" % rc)
-            e.rc = rc
-            raise e
-        self.h = h
-
-    def kind(self):
-        return self.lib.brc_select_kind().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.brc_select_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, EXPORTS, LIB, NAME = "brc_select", SELECT_EXPORTS, SELECT_LIB, "select"
+    PROTOS = {"brc_select_workspace": (C.c_int64, [C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.c_int64]),
+              "brc_select_sites": (C.c_int, [C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(SelectParams), C.c_int64, C.c_int64, C.c_int64] +
+                                   [C.c_void_p] * 5)}
 
     def workspace(self, view, indels, n):
         """bytes of scratch a selection over n positions of the views needs"""
-        return int(self.lib.brc_select_workspace(C.byref(view) if view is not None else None, C.byref(indels) if indels is not None else None, n))
+        return int(self.lib.brc_select_workspace(_ref(view), _ref(indels), n))
 
     def sites_raw(self, view, indels, params, k0, n, cap=0, idx=None, why=None, counts=None, workspace=None, stream=None):
         """brc_select_sites as it is: scratch and destinations are addresses (or None) in memory of the views' kind; returns the code."""
-        return self.lib.brc_select_sites(self.h, C.byref(view) if view is not None else None, C.byref(indels) if indels is not None else None,
-                                         C.byref(params) if params is not None else None, k0, n, cap, idx, why, counts, workspace, stream)
+        return self.lib.brc_select_sites(self.h, _ref(view), _ref(indels), _ref(params), k0, n, cap, idx, why, counts, workspace, stream)
 
     def sites(self, view, indels, params, k0, n, **kw):
-        rc = self.sites_raw(view, indels, params, k0, n, **kw)
-        if rc != 0:
-            raise BrcError("brc_select_sites: %d (%s)" % (rc, self.lib.brc_select_last_error(self.h).decode()))
+        self._check("brc_select_sites", self.sites_raw(view, indels, params, k0, n, **kw))
 
     def last_timing(self):
         """kernel seconds (waits for the launches of the last selection), bytes asked for and scratch bytes written"""
-        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
-        self.lib.brc_select_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
-        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+        return super().last_timing()
 
 
 # ---------------------------------------------------------------- device-side window summaries (include/brc_bins.h)
@@ -1072,64 +912,23 @@ def bins_params(width=0, edges=None, n_bins=0, thresholds=(), n_hist=0):
     return p
 
 
-class Bins:
+class Bins(_Handle):
     """One handle of a library exporting include/brc_bins.h: the product's libbrc_bins_hip.so (default; raises when it is not built or
     there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_bins).  reduce() takes raw
     addresses; bam_readcount_amd.tensors.bins() is the interface that allocates and returns arrays."""
 
-    def __init__(self, path=None, device=0):
-        path = path or BINS_LIB
-        if not os.path.exists(path):
-            raise BrcError("bins library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
-        self.path = path
-        self.lib = L = _load(path)
-        for s in BINS_EXPORTS:
-            if not hasattr(L, s):
-                raise BrcError("%s does not export %s" % (path, s))
-        L.brc_bins_kind.restype = C.c_char_p
-        L.brc_bins_last_error.restype = C.c_char_p; L.brc_bins_last_error.argtypes = [C.c_void_p]
-        L.brc_bins_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.brc_bins_destroy.argtypes = [C.c_void_p]; L.brc_bins_destroy.restype = None
-        L.brc_bins_reduce.argtypes = ([C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(BinsParams), C.c_int64, C.c_int64] +
-                                      [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p])
-        L.brc_bins_last_timing.restype = None
-        L.brc_bins_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        self.device = device
-        h = C.c_void_p()
-        rc = L.brc_bins_create(device, C.byref(h))
-        if rc != 0:
-            e = BrcError("brc_bins_create failed: %d" % rc)
-            e.rc = rc
-            raise e
-        self.h = h
-
-    def kind(self):
-        return self.lib.brc_bins_kind().decode()
-
-    def close(self):
-        if self.h:
-            self.lib.brc_bins_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    PREFIX, EXPORTS, LIB, NAME = "brc_bins", BINS_EXPORTS, BINS_LIB, "bins"
+    PROTOS = {"brc_bins_reduce": (C.c_int, [C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(BinsParams), C.c_int64, C.c_int64] +
+                                  [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_void_p])}
 
     def reduce_raw(self, view, indels, params, k0, n, dst_stride, sums=None, covered=None, hist=None, status=None, stream=None):
         """brc_bins_reduce as it is: destinations and the status word are addresses (or None) in memory of the views' kind; returns the
         code."""
-        return self.lib.brc_bins_reduce(self.h, C.byref(view) if view is not None else None, C.byref(indels) if indels is not None else None,
-                                        C.byref(params) if params is not None else None, k0, n, sums, covered, hist, dst_stride, status, stream)
+        return self.lib.brc_bins_reduce(self.h, _ref(view), _ref(indels), _ref(params), k0, n, sums, covered, hist, dst_stride, status, stream)
 
     def reduce(self, view, indels, params, k0, n, dst_stride, **kw):
-        rc = self.reduce_raw(view, indels, params, k0, n, dst_stride, **kw)
-        if rc != 0:
-            raise BrcError("brc_bins_reduce: %d (%s)" % (rc, self.lib.brc_bins_last_error(self.h).decode()))
+        self._check("brc_bins_reduce", self.reduce_raw(view, indels, params, k0, n, dst_stride, **kw))
 
     def last_timing(self):
         """kernel seconds (waits for the launches of the last reduction), bytes asked for and destination bytes cleared"""
-        k = C.c_double(); r = C.c_uint64(); w = C.c_uint64()
-        self.lib.brc_bins_last_timing(self.h, C.byref(k), C.byref(r), C.byref(w))
-        return dict(kernel_s=k.value, bytes_read=r.value, bytes_written=w.value)
+        return super().last_timing()

@@ -18,10 +18,8 @@
 // build the tests run.  DESIGN.md 6g has the reasoning.
 #include <hip/hip_runtime.h>
 
-#include <new>
-#include <string>
-
 #include "brc_bins_core.h"
+#include "brc_side_hip.h"
 
 using namespace brcbins;
 
@@ -126,96 +124,37 @@ __global__ __launch_bounds__(BLOCK) void k_bins_planes(const Job J) {
     }
 }
 
-struct brc_bins {
-    int device = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    uint64_t bytes_read = 0, bytes_written = 0;
-    std::string err;
-};
-
-#define HIPOK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); return BRC_E_HIP; } } while (0)
+struct brc_bins : brcside::Handle {};
 
 extern "C" {
 
 const char* brc_bins_kind(void) { return "hip-gfx950"; }
-
-void brc_bins_destroy(brc_bins* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    delete h;
-}
-
-int brc_bins_create(int device, brc_bins** out) {
-    if (!out) return BRC_E_ARG;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) { (void)hipGetLastError(); return BRC_E_NODEVICE; }
-    brc_bins* h = new (std::nothrow) brc_bins();
-    if (!h) return BRC_E_NOMEM;
-    h->device = device;
-    hipFuncAttributes fa;
-    if (hipSetDevice(device) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-        hipFuncGetAttributes(&fa, (const void*)k_bins_planes) != hipSuccess) {
-        (void)hipGetLastError(); brc_bins_destroy(h); return BRC_E_NODEVICE;       // (no kernel for this device either: nothing falls back)
-    }
-    *out = h;
-    return BRC_OK;
-}
-
-const char* brc_bins_last_error(const brc_bins* h) { return h ? h->err.c_str() : ""; }
+int brc_bins_create(int device, brc_bins** out) { return brcside::create(device, (const void*)k_bins_planes, out); }
+void brc_bins_destroy(brc_bins* h) { brcside::destroy(h); }
+const char* brc_bins_last_error(const brc_bins* h) { return brcside::last_error(h); }
+void brc_bins_last_timing(const brc_bins* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) { brcside::last_timing(h, kernel_s, bytes_read, bytes_written); }
 
 int brc_bins_reduce(brc_bins* h, const brc_device_view* v, const brc_device_indels* d, const brc_bins_params* p, int64_t k0, int64_t n,
                     uint64_t* sums, uint64_t* covered, uint64_t* hist, int64_t dst_stride, uint32_t* status, void* stream_) {
     if (!h) return BRC_E_ARG;
-    h->err.clear(); h->timed = false; h->bytes_read = h->bytes_written = 0;
+    brcside::clear(h);
     const char* why = "";
-    if (check_job(v, d, p, k0, n, dst_stride, &why)) { h->err = why; return BRC_E_ARG; }
-    if (v->memory != BRC_MEM_DEVICE) { h->err = "the views do not lie in device memory"; return BRC_E_ARG; }
-    if (v->device != h->device) { h->err = "the views lie on another device"; return BRC_E_ARG; }
+    if (check_job(v, d, p, k0, n, dst_stride, &why)) return brcside::refuse(h, why);
+    if (int rc = brcside::resident(h, v, brcside::TWO_VIEWS)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     HIPOK(hipSetDevice(h->device));
     const Job J = make_job(v, d, p, k0, n, dst_stride, sums, covered, hist, status);
     if (!wants_sums(J) && !wants_cov(J) && !wants_hist(J) && !status) return BRC_OK;
-    HIPOK(hipEventRecord(h->ev0, stream));
+    if (int rc = brcside::start(h, stream)) return rc;
     const uint64_t cb = blocks_of(clear_total(J));
-    hipLaunchKernelGGL(k_bins_clear, dim3((unsigned)(cb < CLEAR_BLOCKS ? cb : CLEAR_BLOCKS)), dim3(BLOCK), 0, stream, J);
-    HIPOK(hipGetLastError());
-    if (J.edges && status) {
-        hipLaunchKernelGGL(k_bins_edges, dim3((unsigned)blocks_of((uint64_t)J.n_bins + 1u)), dim3(BLOCK), 0, stream, J);
-        HIPOK(hipGetLastError());
-    }
+    LAUNCH(k_bins_clear, dim3((unsigned)(cb < CLEAR_BLOCKS ? cb : CLEAR_BLOCKS)), dim3(BLOCK), 0, stream, J);
+    if (J.edges && status) LAUNCH(k_bins_edges, dim3((unsigned)blocks_of((uint64_t)J.n_bins + 1u)), dim3(BLOCK), 0, stream, J);
     if (sweeps(J)) {
-        hipLaunchKernelGGL(k_bins_planes, dim3((unsigned)blocks_of((uint64_t)n), (unsigned)J.Lp), dim3(BLOCK),
-                           wants_hist(J) ? (size_t)J.n_hist * sizeof(uint32_t) : 0, stream, J);
-        HIPOK(hipGetLastError());
-        if (walks_records(J)) {
-            hipLaunchKernelGGL(k_bins_records, dim3((unsigned)blocks_of(J.n_xagg)), dim3(BLOCK), 0, stream, J);
-            HIPOK(hipGetLastError());
-        }
-        if (walks_slots(J)) {
-            hipLaunchKernelGGL(k_bins_indels, dim3((unsigned)blocks_of(J.n_slots)), dim3(BLOCK), 0, stream, J);
-            HIPOK(hipGetLastError());
-        }
+        LAUNCH(k_bins_planes, dim3((unsigned)blocks_of((uint64_t)n), (unsigned)J.Lp), dim3(BLOCK), wants_hist(J) ? (size_t)J.n_hist * sizeof(uint32_t) : 0, stream, J);
+        if (walks_records(J)) LAUNCH(k_bins_records, dim3((unsigned)blocks_of(J.n_xagg)), dim3(BLOCK), 0, stream, J);
+        if (walks_slots(J)) LAUNCH(k_bins_indels, dim3((unsigned)blocks_of(J.n_slots)), dim3(BLOCK), 0, stream, J);
     }
-    HIPOK(hipEventRecord(h->ev1, stream));
-    h->timed = true;
-    job_bytes(J, &h->bytes_read, &h->bytes_written);
-    return BRC_OK;
-}
-
-void brc_bins_last_timing(const brc_bins* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) {
-    if (!h) return;
-    double s = 0;
-    if (h->timed && kernel_s) {
-        float ms = 0;
-        if (hipEventSynchronize(h->ev1) == hipSuccess && hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) s = ms * 1e-3; else (void)hipGetLastError();
-    }
-    if (kernel_s) *kernel_s = s;
-    if (bytes_read) *bytes_read = h->bytes_read;
-    if (bytes_written) *bytes_written = h->bytes_written;
+    return brcside::done(h, stream, J);
 }
 
 }  // extern "C"

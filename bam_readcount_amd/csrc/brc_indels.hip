@@ -10,10 +10,8 @@
 // and their lanes read M from the scratch.  DESIGN.md 6d has the reasoning.
 #include <hip/hip_runtime.h>
 
-#include <new>
-#include <string>
-
 #include "brc_indels_core.h"
+#include "brc_side_hip.h"
 
 using namespace brcindels;
 
@@ -93,70 +91,34 @@ __global__ __launch_bounds__(BLOCK) void k_scan_apply(const uint32_t* __restrict
     if (count == 0 && i == 0) out[0] = 0u;
 }
 
-struct brc_indels {
-    int device = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    uint64_t bytes_read = 0, bytes_written = 0;
-    std::string err;
-};
-
-#define HIPOK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); return BRC_E_HIP; } } while (0)
+struct brc_indels : brcside::Handle {};
 
 // the three launches of one scan: `in` [n_host at the most; *n_dev of them when n_dev] -> out [count + 1]
 static int scan(brc_indels* h, hipStream_t stream, const Job& J, const uint32_t* in, const uint32_t* n_dev, uint64_t n_host, uint32_t* out, uint32_t* tot_ws, uint32_t* tot_dst) {
     const uint64_t nb = scan_blocks(n_host);
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(BLOCK), 0, stream, in, n_dev, n_host, J.part);
-    HIPOK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(BLOCK), 0, stream, J.part, nb, tot_ws, tot_dst);
-    HIPOK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(BLOCK), 0, stream, in, n_dev, n_host, (const uint32_t*)J.part, out);
-    HIPOK(hipGetLastError());
+    LAUNCH(k_scan_reduce, dim3((unsigned)nb), dim3(BLOCK), 0, stream, in, n_dev, n_host, J.part);
+    LAUNCH(k_scan_parts, dim3(1), dim3(BLOCK), 0, stream, J.part, nb, tot_ws, tot_dst);
+    LAUNCH(k_scan_apply, dim3((unsigned)nb), dim3(BLOCK), 0, stream, in, n_dev, n_host, (const uint32_t*)J.part, out);
     return BRC_OK;
 }
 
 extern "C" {
 
 const char* brc_indels_kind(void) { return "hip-gfx950"; }
-
-void brc_indels_destroy(brc_indels* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    delete h;
-}
-
-int brc_indels_create(int device, brc_indels** out) {
-    if (!out) return BRC_E_ARG;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) { (void)hipGetLastError(); return BRC_E_NODEVICE; }
-    brc_indels* h = new (std::nothrow) brc_indels();
-    if (!h) return BRC_E_NOMEM;
-    h->device = device;
-    hipFuncAttributes fa;
-    if (hipSetDevice(device) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-        hipFuncGetAttributes(&fa, (const void*)k_emit) != hipSuccess) {
-        (void)hipGetLastError(); brc_indels_destroy(h); return BRC_E_NODEVICE;     // (no kernel for this device either: nothing falls back)
-    }
-    *out = h;
-    return BRC_OK;
-}
-
-const char* brc_indels_last_error(const brc_indels* h) { return h ? h->err.c_str() : ""; }
-
+int brc_indels_create(int device, brc_indels** out) { return brcside::create(device, (const void*)k_emit, out); }
+void brc_indels_destroy(brc_indels* h) { brcside::destroy(h); }
+const char* brc_indels_last_error(const brc_indels* h) { return brcside::last_error(h); }
+void brc_indels_last_timing(const brc_indels* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) { brcside::last_timing(h, kernel_s, bytes_read, bytes_written); }
 size_t brc_indels_workspace(const brc_device_indels* v, int64_t n) { return workspace_bytes(v, n); }
 
 int brc_indels_gather(brc_indels* h, const brc_device_indels* v, int64_t k0, int64_t n, void* workspace, size_t workspace_bytes_, uint32_t* counts,
                       int64_t cap, int64_t alleles_cap, int32_t* pos, int32_t* lib, int32_t* len, uint32_t* rep_read, int32_t* rep_qpos,
                       uint32_t* istat, float* fstat, float* metrics, uint32_t* allele_off, uint8_t* alleles, void* stream_) {
     if (!h) return BRC_E_ARG;
-    h->err.clear(); h->timed = false; h->bytes_read = h->bytes_written = 0;
+    brcside::clear(h);
     const char* why = "";
-    if (check_job(v, k0, n, cap, alleles_cap, workspace, workspace_bytes_, &why)) { h->err = why; return BRC_E_ARG; }
-    if (v->memory != BRC_MEM_DEVICE) { h->err = "the view does not lie in device memory"; return BRC_E_ARG; }
-    if (v->device != h->device) { h->err = "the view lies on another device"; return BRC_E_ARG; }
+    if (check_job(v, k0, n, cap, alleles_cap, workspace, workspace_bytes_, &why)) return brcside::refuse(h, why);
+    if (int rc = brcside::resident(h, v, brcside::ONE_VIEW)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     HIPOK(hipSetDevice(h->device));
     if (n == 0 || v->n_slots == 0) {
@@ -167,38 +129,17 @@ int brc_indels_gather(brc_indels* h, const brc_device_indels* v, int64_t k0, int
     const Job J = make_job(v, k0, n, workspace, counts, cap, alleles_cap, pos, lib, len, rep_read, rep_qpos, istat, fstat, metrics, allele_off, alleles);
     if (!counts && !wants_records(J)) return BRC_OK;
     const unsigned slot_blocks = (unsigned)scan_blocks(J.n_slots);
-    HIPOK(hipEventRecord(h->ev0, stream));
+    if (int rc = brcside::start(h, stream)) return rc;
     HIPOK(hipMemsetAsync(J.cnt, 0, (size_t)n * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(k_count, dim3(slot_blocks), dim3(BLOCK), 0, stream, J);
-    HIPOK(hipGetLastError());
+    LAUNCH(k_count, dim3(slot_blocks), dim3(BLOCK), 0, stream, J);
     int rc = scan(h, stream, J, J.cnt, nullptr, (uint64_t)n, J.off, J.tot, counts);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_place, dim3(slot_blocks), dim3(BLOCK), 0, stream, J);
-    HIPOK(hipGetLastError());
-    hipLaunchKernelGGL(k_rank, dim3(slot_blocks), dim3(BLOCK), 0, stream, J);
-    HIPOK(hipGetLastError());
+    LAUNCH(k_place, dim3(slot_blocks), dim3(BLOCK), 0, stream, J);
+    LAUNCH(k_rank, dim3(slot_blocks), dim3(BLOCK), 0, stream, J);
     rc = scan(h, stream, J, J.alen, J.tot, J.n_slots, J.aoff, J.tot + 1, counts ? counts + 1 : nullptr);
     if (rc) return rc;
-    if (wants_records(J)) {
-        hipLaunchKernelGGL(k_emit, dim3((unsigned)scan_blocks(J.n_slots + 1)), dim3(BLOCK), 0, stream, J);
-        HIPOK(hipGetLastError());
-    }
-    HIPOK(hipEventRecord(h->ev1, stream));
-    h->timed = true;
-    job_bytes(J, &h->bytes_read, &h->bytes_written);
-    return BRC_OK;
-}
-
-void brc_indels_last_timing(const brc_indels* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) {
-    if (!h) return;
-    double s = 0;
-    if (h->timed && kernel_s) {
-        float ms = 0;
-        if (hipEventSynchronize(h->ev1) == hipSuccess && hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) s = ms * 1e-3; else (void)hipGetLastError();
-    }
-    if (kernel_s) *kernel_s = s;
-    if (bytes_read) *bytes_read = h->bytes_read;
-    if (bytes_written) *bytes_written = h->bytes_written;
+    if (wants_records(J)) LAUNCH(k_emit, dim3((unsigned)scan_blocks(J.n_slots + 1)), dim3(BLOCK), 0, stream, J);
+    return brcside::done(h, stream, J);
 }
 
 }  // extern "C"

@@ -14,10 +14,8 @@
 // k_select_parts.  The per-lane work is brc_select_core.h, shared with the CPU build the tests run.  DESIGN.md 6f has the reasoning.
 #include <hip/hip_runtime.h>
 
-#include <new>
-#include <string>
-
 #include "brc_select_core.h"
+#include "brc_side_hip.h"
 
 using namespace brcselect;
 
@@ -96,57 +94,24 @@ __global__ __launch_bounds__(BLOCK) void k_select_emit(const Job J) {
     emit_lane(J, j, why, at);
 }
 
-struct brc_select {
-    int device = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    uint64_t bytes_read = 0, bytes_written = 0;
-    std::string err;
-};
-
-#define HIPOK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); return BRC_E_HIP; } } while (0)
+struct brc_select : brcside::Handle {};
 
 extern "C" {
 
 const char* brc_select_kind(void) { return "hip-gfx950"; }
-
-void brc_select_destroy(brc_select* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    delete h;
-}
-
-int brc_select_create(int device, brc_select** out) {
-    if (!out) return BRC_E_ARG;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) { (void)hipGetLastError(); return BRC_E_NODEVICE; }
-    brc_select* h = new (std::nothrow) brc_select();
-    if (!h) return BRC_E_NOMEM;
-    h->device = device;
-    hipFuncAttributes fa;
-    if (hipSetDevice(device) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-        hipFuncGetAttributes(&fa, (const void*)k_select_why) != hipSuccess) {
-        (void)hipGetLastError(); brc_select_destroy(h); return BRC_E_NODEVICE;     // (no kernel for this device either: nothing falls back)
-    }
-    *out = h;
-    return BRC_OK;
-}
-
-const char* brc_select_last_error(const brc_select* h) { return h ? h->err.c_str() : ""; }
-
+int brc_select_create(int device, brc_select** out) { return brcside::create(device, (const void*)k_select_why, out); }
+void brc_select_destroy(brc_select* h) { brcside::destroy(h); }
+const char* brc_select_last_error(const brc_select* h) { return brcside::last_error(h); }
+void brc_select_last_timing(const brc_select* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) { brcside::last_timing(h, kernel_s, bytes_read, bytes_written); }
 int64_t brc_select_workspace(const brc_device_view* v, const brc_device_indels*, int64_t n) { return workspace_bytes(v, n); }
 
 int brc_select_sites(brc_select* h, const brc_device_view* v, const brc_device_indels* d, const brc_select_params* p, int64_t k0, int64_t n, int64_t cap,
                      int32_t* idx, uint32_t* why_, uint32_t* counts, void* workspace, void* stream_) {
     if (!h) return BRC_E_ARG;
-    h->err.clear(); h->timed = false; h->bytes_read = h->bytes_written = 0;
+    brcside::clear(h);
     const char* why = "";
-    if (check_job(v, d, p, k0, n, cap, workspace, &why)) { h->err = why; return BRC_E_ARG; }
-    if (v->memory != BRC_MEM_DEVICE) { h->err = "the views do not lie in device memory"; return BRC_E_ARG; }
-    if (v->device != h->device) { h->err = "the views lie on another device"; return BRC_E_ARG; }
+    if (check_job(v, d, p, k0, n, cap, workspace, &why)) return brcside::refuse(h, why);
+    if (int rc = brcside::resident(h, v, brcside::TWO_VIEWS)) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     HIPOK(hipSetDevice(h->device));
     if (n == 0) {
@@ -156,41 +121,19 @@ int brc_select_sites(brc_select* h, const brc_device_view* v, const brc_device_i
     const Job J = make_job(v, d, p, k0, n, cap, idx, why_, counts, workspace);
     if (!counts && !wants_list(J)) return BRC_OK;
     const unsigned nb = (unsigned)blocks_of((uint64_t)n);
-    HIPOK(hipEventRecord(h->ev0, stream));
+    if (int rc = brcside::start(h, stream)) return rc;
     if (walks_records(J)) {
         HIPOK(hipMemsetAsync(J.head, 0xff, (size_t)n * sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(k_select_link, dim3((unsigned)blocks_of(J.n_xagg)), dim3(BLOCK), 0, stream, J);
-        HIPOK(hipGetLastError());
+        LAUNCH(k_select_link, dim3((unsigned)blocks_of(J.n_xagg)), dim3(BLOCK), 0, stream, J);
     }
     if (walks_slots(J)) {
         HIPOK(hipMemsetAsync(J.flag, 0, (size_t)n * sizeof(uint32_t), stream));
-        hipLaunchKernelGGL(k_select_flag, dim3((unsigned)blocks_of(J.n_slots)), dim3(BLOCK), 0, stream, J);
-        HIPOK(hipGetLastError());
+        LAUNCH(k_select_flag, dim3((unsigned)blocks_of(J.n_slots)), dim3(BLOCK), 0, stream, J);
     }
-    hipLaunchKernelGGL(k_select_why, dim3(nb), dim3(BLOCK), 0, stream, J);
-    HIPOK(hipGetLastError());
-    hipLaunchKernelGGL(k_select_parts, dim3(1), dim3(BLOCK), 0, stream, J, (uint64_t)nb);
-    HIPOK(hipGetLastError());
-    if (wants_list(J)) {
-        hipLaunchKernelGGL(k_select_emit, dim3(nb), dim3(BLOCK), 0, stream, J);
-        HIPOK(hipGetLastError());
-    }
-    HIPOK(hipEventRecord(h->ev1, stream));
-    h->timed = true;
-    job_bytes(J, &h->bytes_read, &h->bytes_written);
-    return BRC_OK;
-}
-
-void brc_select_last_timing(const brc_select* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) {
-    if (!h) return;
-    double s = 0;
-    if (h->timed && kernel_s) {
-        float ms = 0;
-        if (hipEventSynchronize(h->ev1) == hipSuccess && hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) s = ms * 1e-3; else (void)hipGetLastError();
-    }
-    if (kernel_s) *kernel_s = s;
-    if (bytes_read) *bytes_read = h->bytes_read;
-    if (bytes_written) *bytes_written = h->bytes_written;
+    LAUNCH(k_select_why, dim3(nb), dim3(BLOCK), 0, stream, J);
+    LAUNCH(k_select_parts, dim3(1), dim3(BLOCK), 0, stream, J, (uint64_t)nb);
+    if (wants_list(J)) LAUNCH(k_select_emit, dim3(nb), dim3(BLOCK), 0, stream, J);
+    return brcside::done(h, stream, J);
 }
 
 }  // extern "C"

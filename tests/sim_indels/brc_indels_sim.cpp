@@ -4,21 +4,12 @@
 // record lane of the emission — on host memory: a view with memory == BRC_MEM_HOST (what libbrc_sim.so hands out).  Slot lanes run
 // from the LAST slot to the first, so that the order inside a position's run is not the slots' own: the rank has to make it.
 // Test infrastructure only.
-#include <chrono>
-#include <new>
-#include <string>
-
 #include "../../bam_readcount_amd/csrc/brc_indels_core.h"
+#include "../sim_side.h"
 
 using namespace brcindels;
 
-struct brc_indels {
-    int device = 0;                 // (host views carry device 0: a handle made for another ordinal refuses them like the hip library would)
-    std::string err;
-    double kernel_s = 0; uint64_t bytes_read = 0, bytes_written = 0;
-};
-
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+struct brc_indels : brcside::Handle {};
 
 // in[0 .. count) -> out[0 .. count]: the exclusive scan and, behind it, the total
 static uint32_t scan(const uint32_t* in, uint64_t count, uint32_t* out) {
@@ -31,26 +22,20 @@ static uint32_t scan(const uint32_t* in, uint64_t count, uint32_t* out) {
 extern "C" {
 
 const char* brc_indels_kind(void) { return "sim"; }
-
-int brc_indels_create(int device, brc_indels** out) {
-    if (!out || device < 0) return BRC_E_ARG;
-    *out = new (std::nothrow) brc_indels();
-    if (*out) (*out)->device = device;
-    return *out ? BRC_OK : BRC_E_NOMEM;
-}
-void brc_indels_destroy(brc_indels* h) { delete h; }
-const char* brc_indels_last_error(const brc_indels* h) { return h ? h->err.c_str() : ""; }
+int brc_indels_create(int device, brc_indels** out) { return brcside::create(device, out); }
+void brc_indels_destroy(brc_indels* h) { brcside::destroy(h); }
+const char* brc_indels_last_error(const brc_indels* h) { return brcside::last_error(h); }
+void brc_indels_last_timing(const brc_indels* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) { brcside::last_timing(h, kernel_s, bytes_read, bytes_written); }
 size_t brc_indels_workspace(const brc_device_indels* v, int64_t n) { return workspace_bytes(v, n); }
 
 int brc_indels_gather(brc_indels* h, const brc_device_indels* v, int64_t k0, int64_t n, void* workspace, size_t workspace_bytes_, uint32_t* counts,
                       int64_t cap, int64_t alleles_cap, int32_t* pos, int32_t* lib, int32_t* len, uint32_t* rep_read, int32_t* rep_qpos,
                       uint32_t* istat, float* fstat, float* metrics, uint32_t* allele_off, uint8_t* alleles, void*) {
     if (!h) return BRC_E_ARG;
-    h->err.clear(); h->kernel_s = 0; h->bytes_read = h->bytes_written = 0;
+    brcside::clear(h);
     const char* why = "";
-    if (check_job(v, k0, n, cap, alleles_cap, workspace, workspace_bytes_, &why)) { h->err = why; return BRC_E_ARG; }
-    if (v->memory != BRC_MEM_HOST) { h->err = "the view does not lie in host memory"; return BRC_E_ARG; }
-    if (v->device != h->device) { h->err = "the view lies on another device"; return BRC_E_ARG; }
+    if (check_job(v, k0, n, cap, alleles_cap, workspace, workspace_bytes_, &why)) return brcside::refuse(h, why);
+    if (int rc = brcside::resident(h, v, brcside::ONE_VIEW)) return rc;
     if (n == 0 || v->n_slots == 0) {
         if (counts) counts[0] = counts[1] = 0;
         if (allele_off) allele_off[0] = 0;
@@ -58,7 +43,7 @@ int brc_indels_gather(brc_indels* h, const brc_device_indels* v, int64_t k0, int
     }
     const Job J = make_job(v, k0, n, workspace, counts, cap, alleles_cap, pos, lib, len, rep_read, rep_qpos, istat, fstat, metrics, allele_off, alleles);
     if (!counts && !wants_records(J)) return BRC_OK;
-    const double t0 = now_s();
+    brcside::start(h);
     for (int64_t d = 0; d < n; ++d) J.cnt[d] = 0;
     for (uint64_t s = J.n_slots; s-- > 0;) count_lane(J, s);
     J.tot[0] = scan(J.cnt, (uint64_t)n, J.off);
@@ -68,16 +53,7 @@ int brc_indels_gather(brc_indels* h, const brc_device_indels* v, int64_t k0, int
     J.tot[1] = scan(J.alen, J.tot[0], J.aoff);
     if (counts) counts[1] = J.tot[1];
     if (wants_records(J)) for (uint64_t r = 0; r <= J.n_slots; ++r) emit_lane(J, r);
-    h->kernel_s = now_s() - t0;
-    job_bytes(J, &h->bytes_read, &h->bytes_written);
-    return BRC_OK;
-}
-
-void brc_indels_last_timing(const brc_indels* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) {
-    if (!h) return;
-    if (kernel_s) *kernel_s = h->kernel_s;
-    if (bytes_read) *bytes_read = h->bytes_read;
-    if (bytes_written) *bytes_written = h->bytes_written;
+    return brcside::done(h, J);
 }
 
 }  // extern "C"

@@ -5,49 +5,34 @@
 // ascending run).  The compaction is a serial loop.  Test infrastructure only.
 #include <string.h>
 
-#include <chrono>
-#include <new>
-#include <string>
-
 #include "../../bam_readcount_amd/csrc/brc_select_core.h"
+#include "../sim_side.h"
 
 using namespace brcselect;
 
-struct brc_select {
-    int device = 0;                 // (host views carry device 0: a handle made for another ordinal refuses them like the hip library would)
-    std::string err;
-    double kernel_s = 0; uint64_t bytes_read = 0, bytes_written = 0;
-};
-
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+struct brc_select : brcside::Handle {};
 
 extern "C" {
 
 const char* brc_select_kind(void) { return "sim"; }
-
-int brc_select_create(int device, brc_select** out) {
-    if (!out || device < 0) return BRC_E_ARG;
-    *out = new (std::nothrow) brc_select();
-    if (*out) (*out)->device = device;
-    return *out ? BRC_OK : BRC_E_NOMEM;
-}
-void brc_select_destroy(brc_select* h) { delete h; }
-const char* brc_select_last_error(const brc_select* h) { return h ? h->err.c_str() : ""; }
+int brc_select_create(int device, brc_select** out) { return brcside::create(device, out); }
+void brc_select_destroy(brc_select* h) { brcside::destroy(h); }
+const char* brc_select_last_error(const brc_select* h) { return brcside::last_error(h); }
+void brc_select_last_timing(const brc_select* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) { brcside::last_timing(h, kernel_s, bytes_read, bytes_written); }
 
 int64_t brc_select_workspace(const brc_device_view* v, const brc_device_indels*, int64_t n) { return workspace_bytes(v, n); }
 
 int brc_select_sites(brc_select* h, const brc_device_view* v, const brc_device_indels* d, const brc_select_params* p, int64_t k0, int64_t n, int64_t cap,
                      int32_t* idx, uint32_t* why_, uint32_t* counts, void* workspace, void*) {
     if (!h) return BRC_E_ARG;
-    h->err.clear(); h->kernel_s = 0; h->bytes_read = h->bytes_written = 0;
+    brcside::clear(h);
     const char* why = "";
-    if (check_job(v, d, p, k0, n, cap, workspace, &why)) { h->err = why; return BRC_E_ARG; }
-    if (v->memory != BRC_MEM_HOST) { h->err = "the views do not lie in host memory"; return BRC_E_ARG; }
-    if (v->device != h->device) { h->err = "the views lie on another device"; return BRC_E_ARG; }
+    if (check_job(v, d, p, k0, n, cap, workspace, &why)) return brcside::refuse(h, why);
+    if (int rc = brcside::resident(h, v, brcside::TWO_VIEWS)) return rc;
     if (n == 0) { if (counts) *counts = 0; return BRC_OK; }
     const Job J = make_job(v, d, p, k0, n, cap, idx, why_, counts, workspace);
     if (!counts && !wants_list(J)) return BRC_OK;
-    const double t0 = now_s();
+    brcside::start(h);
     if (walks_records(J)) {
         memset(J.head, 0xff, (size_t)n * sizeof(uint32_t));
         for (uint64_t r = J.n_xagg; r-- > 0;) link_lane(J, r);
@@ -74,16 +59,7 @@ int brc_select_sites(brc_select* h, const brc_device_view* v, const brc_device_i
             for (int64_t j = (int64_t)b * BLOCK; j < n && j < (int64_t)(b + 1) * BLOCK; ++j) { emit_lane(J, j, J.flag[j], at); at += J.flag[j] != 0u; }
         }
     }
-    h->kernel_s = now_s() - t0;
-    job_bytes(J, &h->bytes_read, &h->bytes_written);
-    return BRC_OK;
-}
-
-void brc_select_last_timing(const brc_select* h, double* kernel_s, uint64_t* bytes_read, uint64_t* bytes_written) {
-    if (!h) return;
-    if (kernel_s) *kernel_s = h->kernel_s;
-    if (bytes_read) *bytes_read = h->bytes_read;
-    if (bytes_written) *bytes_written = h->bytes_written;
+    return brcside::done(h, J);
 }
 
 }  // extern "C"
