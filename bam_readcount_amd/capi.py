@@ -932,3 +932,62 @@ class Bins(_Handle):
     def last_timing(self):
         """kernel seconds (waits for the launches of the last reduction), bytes asked for and destination bytes cleared"""
         return super().last_timing()
+
+
+# ---------------------------------------------------------------- device-side depth-class intervals (include/brc_runs.h)
+RUNS_LIB = os.path.join(HERE, "csrc", "libbrc_runs_hip.so")
+RUNS_EXPORTS = [
+    "brc_runs_create", "brc_runs_destroy", "brc_runs_kind", "brc_runs_last_error", "brc_runs_workspace", "brc_runs_find", "brc_runs_last_timing",
+]
+RUNS_MAX_LIB, RUNS_MAX_CUT = 254, 15
+RUNS_MIN, RUNS_MAX, RUNS_SUM = 0, 1, 2
+RUNS_REF_N = 1
+
+
+class RunsParams(C.Structure):
+    """brc_runs_params (include/brc_runs.h)"""
+    _fields_ = [("role", C.c_void_p), ("combine", C.c_uint32), ("n_cut", C.c_uint32), ("cut", C.c_uint32 * RUNS_MAX_CUT), ("keep", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+def runs_params(cuts, combine=RUNS_MIN, role=None, keep=None, flags=0):
+    """(RunsParams, keepalive): cuts is a sequence of depths (strictly ascending, 1 .. RUNS_MAX_CUT of them), role a sequence of 0 (ignored)
+    / 1 (counted) per library or None (every library counts), keep the bit mask of the classes whose runs are written (None: every class
+    the call can produce)"""
+    cuts = list(cuts)
+    p = RunsParams(None, combine, len(cuts))
+    for i, x in enumerate(cuts[:RUNS_MAX_CUT]):
+        p.cut[i] = x
+    p.keep = (1 << (len(cuts) + (2 if flags & RUNS_REF_N else 1))) - 1 if keep is None else keep
+    p.flags = flags
+    keepalive = None
+    if role is not None:
+        keepalive = np.ascontiguousarray(role, np.uint8)
+        p.role = keepalive.ctypes.data
+    return p, keepalive
+
+
+class Runs(_Handle):
+    """One handle of a library exporting include/brc_runs.h: the product's libbrc_runs_hip.so (default; raises when it is not built or
+    there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_runs).  find() takes raw
+    addresses; bam_readcount_amd.tensors.runs() is the interface that allocates and returns arrays."""
+
+    PREFIX, EXPORTS, LIB, NAME = "brc_runs", RUNS_EXPORTS, RUNS_LIB, "runs"
+    PROTOS = {"brc_runs_workspace": (C.c_int64, [C.c_int64]),
+              "brc_runs_find": (C.c_int, [C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(RunsParams), C.c_int64, C.c_int64, C.c_int64] +
+                                [C.c_void_p] * 7)}
+
+    def workspace(self, n):
+        """bytes of scratch a call over n positions needs"""
+        return int(self.lib.brc_runs_workspace(n))
+
+    def find_raw(self, view, indels, params, k0, n, cap=0, start=None, end=None, cls=None, counts=None, per_class=None, workspace=None, stream=None):
+        """brc_runs_find as it is: scratch and destinations are addresses (or None) in memory of the view's kind; returns the code."""
+        return self.lib.brc_runs_find(self.h, _ref(view), _ref(indels), _ref(params), k0, n, cap, start, end, cls, counts, per_class, workspace, stream)
+
+    def find(self, view, indels, params, k0, n, **kw):
+        self._check("brc_runs_find", self.find_raw(view, indels, params, k0, n, **kw))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last call), bytes asked for and scratch bytes written"""
+        return super().last_timing()

@@ -29,6 +29,11 @@ a deletion) in "case" libraries and none in "control" libraries, found by libbrc
 Per-window questions — depth, coverage at thresholds, allele and indel load per bin and library, a depth histogram — are answered by
 bins(): exact integer sums over uniform bins or an edge list, reduced by libbrc_bins_hip.so (capi.Bins) without a synchronisation:
     cov = tensors.bins(eng, capi.Bins(), width=1000, thresholds=(10, 20, 30), hist=256)
+
+Where the stretches are — the maximal intervals over which coverage stays in one class: callable in every library, below 10x in the
+normal, no coverage, reference is N — is answered by runs(): an ascending list of intervals with a class each, found by
+libbrc_runs_hip.so (capi.Runs) over the depth planes; its starts and ends are edges for bins() and masks for select()'s list:
+    ok = tensors.runs(eng, capi.Runs(), cuts=(10,), combine="min", keep=(1,), ref_n=True)       # >= 10x in every library, reference known
 """
 import numpy as np
 
@@ -528,3 +533,120 @@ def bins(engine, bins, *, width=None, edges=None, thresholds=(), hist=0, beg0=No
         res["start"] = start
     res.update(arrays)
     return res
+
+
+RUNS_COMBINE = {"min": capi.RUNS_MIN, "max": capi.RUNS_MAX, "sum": capi.RUNS_SUM}
+
+
+def _counted(engine, n_lib, libs):
+    """libs (library names of the engine, or library numbers) -> uint8 [n_lib] of 0 / 1, or None: every library counts"""
+    if libs is None:
+        return None
+    given = [libs] if isinstance(libs, (str, bytes)) else list(libs)
+    if not given:
+        raise ValueError("no library is counted")
+    r = np.zeros(n_lib, np.uint8)
+    names = None
+    for x in given:
+        if isinstance(x, (str, bytes)):
+            if names is None:
+                names = [b.decode() for b in engine._names]
+                if len(names) != n_lib:
+                    raise ValueError("libs names libraries: the engine reports one set of counts for all of them")
+            x = x.decode() if isinstance(x, bytes) else x
+            if x not in names:
+                raise ValueError("%r is not a library of the engine (%r)" % (x, names))
+            l = names.index(x)
+        else:
+            if isinstance(x, bool) or int(x) != x or not 0 <= int(x) < n_lib:
+                raise ValueError("libs: library names or numbers in [0, %d)" % n_lib)
+            l = int(x)
+        if r[l]:
+            raise ValueError("library %r is named twice" % (x,))
+        r[l] = 1
+    return r
+
+
+def runs(engine, runs, *, cuts, combine="min", libs=None, keep=None, ref_n=False, beg0=None, end=None):
+    """The maximal intervals of [beg0, end) of the engine's last computed region (clipped as region() clips) over which the depth class
+    is constant — include/brc_runs.h has the exact definition:
+      V = the minimum ("min"), maximum ("max") or sum ("sum", in 64 bits) of the depth over the counted libraries; class = the number
+      of cuts <= V, 0 .. len(cuts); with ref_n a position whose reference character is none of ACGTacgt has class len(cuts) + 1.
+    cuts: 1 .. capi.RUNS_MAX_CUT depths, strictly ascending.  libs: the counted libraries, by the engine's library names or by number
+    (None: all of them).  keep: the classes whose intervals are returned (None: all).
+
+    Returns {"n": the number of intervals, "k0", "k1": int32 [n] plane indices [k0[j], k1[j]), ascending and disjoint, "start", "end":
+    int32 [n] the same as reference positions pos0 + k, "cls": int32 [n] the class of each, "per_class": uint64 [n_class] the number of
+    positions of each class in the window whatever keep is, "n_class": len(cuts) + 2}.  With the HIP libraries the arrays are torch
+    tensors on the engine's device, filled on torch's current stream, the scratch comes from torch.empty; with the CPU builds they are
+    numpy arrays.  "start" / "end" interleaved are what bins(edges=...) takes.
+
+    SYNCHRONISES ONCE: the list's length is data.  A first call asks for the count and per_class alone, the host reads the count (as
+    torch.nonzero does), then the list is allocated exactly and a second call fills it without another wait.
+    ValueError for parameters the library would refuse, before anything is queued."""
+    if combine not in RUNS_COMBINE:
+        raise ValueError("combine: one of %r" % (sorted(RUNS_COMBINE),))
+    try:
+        cut = [_u32(c, "a cut") for c in cuts]
+    except TypeError:
+        raise ValueError("cuts: a sequence of integers")
+    if not 1 <= len(cut) <= capi.RUNS_MAX_CUT:
+        raise ValueError("cuts: 1 .. %d depths" % capi.RUNS_MAX_CUT)
+    if any(b <= a for a, b in zip(cut, cut[1:])):
+        raise ValueError("the cuts must ascend strictly")
+    n_class = len(cut) + 2
+    if keep is None:
+        mask = (1 << (n_class if ref_n else n_class - 1)) - 1
+    else:
+        mask = 0
+        for c in ([keep] if isinstance(keep, int) and not isinstance(keep, bool) else list(keep)):
+            if isinstance(c, bool) or int(c) != c or not 0 <= int(c) < n_class:
+                raise ValueError("keep: classes in [0, %d)" % n_class)
+            mask |= 1 << int(c)
+        if not mask:
+            raise ValueError("keep is empty: no class would be returned")
+    v = engine.device_view()
+    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    if L > capi.RUNS_MAX_LIB:
+        raise ValueError("runs takes at most %d libraries" % capi.RUNS_MAX_LIB)
+    d = None
+    if ref_n:
+        try:
+            d = engine.device_indels()
+        except capi.BrcError as e:
+            raise ValueError("ref_n needs the engine's indels view, which carries the reference: %s" % e)
+    params, keepalive = capi.runs_params(cut, RUNS_COMBINE[combine], _counted(engine, L, libs), mask, capi.RUNS_REF_N if ref_n else 0)
+    lo = pos0 if beg0 is None else max(int(beg0), pos0)
+    hi = pos0 + P if end is None else min(int(end), pos0 + P)
+    lo = min(lo, pos0 + P)
+    n = max(hi - lo, 0)
+    k0 = lo - pos0 if n else 0
+    wsb = runs.workspace(n)
+    if v.memory == capi.MEM_HOST:
+        def empty(m):
+            return np.empty(m, np.int32)
+        ptr, stream = (lambda a: a.ctypes.data), None
+        counts = np.zeros(1, np.int32)
+        per = np.zeros(n_class, np.uint64)
+    elif v.memory == capi.MEM_DEVICE:
+        import torch          # (lazily: the package and its CPU route work without torch)
+        dev = torch.device("cuda", int(v.device))
+
+        def empty(m):
+            return torch.empty(m, dtype=torch.int32, device=dev)
+        ptr = lambda a: a.data_ptr()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+        counts = torch.zeros(1, dtype=torch.int32, device=dev)
+        per = torch.zeros(n_class, dtype=torch.int64, device=dev).view(torch.uint64)
+    else:
+        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
+    ws = empty(max(wsb // 4, 1))
+    runs.find(v, d, params, k0, n, counts=ptr(counts), per_class=ptr(per), workspace=ptr(ws), stream=stream)
+    m = int(counts[0]) & 0xFFFFFFFF                                       # the one wait
+    a, b, c = empty(m), empty(m), empty(m)
+    if m:
+        runs.find(v, d, params, k0, n, cap=m, start=ptr(a), end=ptr(b), cls=ptr(c), workspace=ptr(ws), stream=stream)
+    del keepalive
+    off = np.int32(pos0) if v.memory == capi.MEM_HOST else pos0
+    return {"n": m, "k0": a, "k1": b, "start": a + off, "end": b + off, "cls": c, "per_class": per, "n_class": n_class}
