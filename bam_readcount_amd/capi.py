@@ -626,6 +626,21 @@ def _ref(x):
 _TIMING5 = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
 
 
+class _Codec(_Handle):
+    """What the two codec classes share on top of _Handle: the (kernel_s, call_s, bytes_in, bytes_out) last_timing() and the prototypes
+    of the page-locked allocator, which carries the library's stem (PREFIX "brc_inflater": brc_inflate_host_alloc, _host_free)."""
+    TIMING = _TIMING5
+
+    def __init_subclass__(cls):
+        stem = cls.PREFIX[:-1]
+        cls.PROTOS = dict(cls.PROTOS, **{stem + "_host_alloc": (C.c_void_p, [C.c_size_t]), stem + "_host_free": (None, [C.c_void_p])})
+
+    def last_timing(self):
+        k = C.c_double(); c = C.c_double(); bi = C.c_uint64(); bo = C.c_uint64()
+        self._call("_last_timing")(self.h, C.byref(k), C.byref(c), C.byref(bi), C.byref(bo))
+        return dict(kernel_s=k.value, call_s=c.value, bytes_in=bi.value, bytes_out=bo.value)
+
+
 # ---------------------------------------------------------------- the BGZF inflater (include/brc_inflate.h)
 INFLATE_LIB = os.path.join(HERE, "csrc", "libbrc_inflate_hip.so")
 INFLATE_EXPORTS = [
@@ -636,13 +651,12 @@ INF_OK, INF_BAD_HEADER, INF_BAD_STREAM, INF_SIZE_MISMATCH, INF_CRC_MISMATCH, INF
 E_ARG, E_NODEVICE = -1, -2
 
 
-class Inflater(_Handle):
+class Inflater(_Codec):
     """One inflater handle of a library exporting include/brc_inflate.h: the product's libbrc_inflate_hip.so (default; raises when it
     is not built or there is no device — nothing falls back) or the CPU build of the same decoder (tests/sim_inflate)."""
 
-    PREFIX, EXPORTS, LIB, NAME, TIMING = "brc_inflater", INFLATE_EXPORTS, INFLATE_LIB, "inflater", _TIMING5
-    PROTOS = {"brc_inflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
-              "brc_inflate_host_alloc": (C.c_void_p, [C.c_size_t]), "brc_inflate_host_free": (None, [C.c_void_p])}
+    PREFIX, EXPORTS, LIB, NAME = "brc_inflater", INFLATE_EXPORTS, INFLATE_LIB, "inflater"
+    PROTOS = {"brc_inflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)])}
 
     def inflate_raw(self, src, dst_cap=None, capacity=None, whole=False):
         """brc_inflate_bgzf as it is: (rc, bytes of dst, dst_off[0..n], statuses[0..n)).  dst_cap / capacity None: sized by a first,
@@ -671,11 +685,6 @@ class Inflater(_Handle):
         self._check("brc_inflate_bgzf", rc)
         return out, off, st
 
-    def last_timing(self):
-        k = C.c_double(); c = C.c_double(); bi = C.c_uint64(); bo = C.c_uint64()
-        self.lib.brc_inflater_last_timing(self.h, C.byref(k), C.byref(c), C.byref(bi), C.byref(bo))
-        return dict(kernel_s=k.value, call_s=c.value, bytes_in=bi.value, bytes_out=bo.value)
-
 
 # ---------------------------------------------------------------- the BGZF deflater (include/brc_deflate.h)
 DEFLATE_LIB = os.path.join(HERE, "csrc", "libbrc_deflate_hip.so")
@@ -686,15 +695,14 @@ DEFLATE_EXPORTS = [
 DEFLATE_MEMBER_INPUT = 0xff00
 
 
-class Deflater(_Handle):
+class Deflater(_Codec):
     """One deflater handle of a library exporting include/brc_deflate.h: the product's libbrc_deflate_hip.so (default; raises when it
     is not built or there is no device — nothing falls back) or the CPU build of the same compressor (tests/sim_deflate)."""
 
-    PREFIX, EXPORTS, LIB, NAME, TIMING = "brc_deflater", DEFLATE_EXPORTS, DEFLATE_LIB, "deflater", _TIMING5
+    PREFIX, EXPORTS, LIB, NAME = "brc_deflater", DEFLATE_EXPORTS, DEFLATE_LIB, "deflater"
     PROTOS = {"brc_deflate_bound": (C.c_size_t, [C.c_size_t]),
               "brc_deflate_bgzf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-              "brc_deflate_eof_block": (C.c_void_p, [C.POINTER(C.c_size_t)]),
-              "brc_deflate_host_alloc": (C.c_void_p, [C.c_size_t]), "brc_deflate_host_free": (None, [C.c_void_p])}
+              "brc_deflate_eof_block": (C.c_void_p, [C.POINTER(C.c_size_t)])}
 
     def bound(self, n):
         return int(self.lib.brc_deflate_bound(n))
@@ -725,11 +733,6 @@ class Deflater(_Handle):
         rc, out, _ = self.deflate_raw(src)
         self._check("brc_deflate_bgzf", rc)
         return out
-
-    def last_timing(self):
-        k = C.c_double(); c = C.c_double(); bi = C.c_uint64(); bo = C.c_uint64()
-        self.lib.brc_deflater_last_timing(self.h, C.byref(k), C.byref(c), C.byref(bi), C.byref(bo))
-        return dict(kernel_s=k.value, call_s=c.value, bytes_in=bi.value, bytes_out=bo.value)
 
 
 # ---------------------------------------------------------------- device-resident results (include/brc_dense.h)

@@ -8,15 +8,11 @@
 // cross PCIe.  DESIGN.md 6b has the reasoning and the measurements.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-#include <mutex>
-#include <new>
-#include <string>
-
 #include <string.h>
 
 #include "brc_deflate_core.h"
 #include "../../include/brc_deflate.h"
+#include "brc_codec_hip.h"
 
 using namespace brcdef;
 
@@ -65,140 +61,61 @@ __global__ __launch_bounds__(LANES) void k_gather(const uint8_t* __restrict__ sl
     if (tail0 + threadIdx.x < sz) d[tail0 + threadIdx.x] = s[tail0 + threadIdx.x];
 }
 
-struct brc_deflater {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    uint8_t *d_src = nullptr, *d_slots = nullptr, *d_out = nullptr; uint32_t* d_sizes = nullptr; uint64_t* d_offs = nullptr;
-    size_t cap_src = 0, cap_slots = 0, cap_out = 0, cap_sizes = 0, cap_offs = 0;
-    uint8_t *h_src = nullptr, *h_dst = nullptr; size_t hcap_src = 0, hcap_dst = 0;     // page-locked staging for callers' pageable memory
+struct brc_deflater : brccodec::Handle {
+    brccodec::DevBuf<uint8_t> d_src, d_slots, d_out; brccodec::DevBuf<uint32_t> d_sizes; brccodec::DevBuf<uint64_t> d_offs;
     uint64_t* h_total = nullptr;                                                          // page-locked: where the scan's last word lands
-    std::mutex mu;
-    std::string err;
-    double kernel_s = 0, call_s = 0; uint64_t bytes_in = 0, bytes_out = 0;
+    ~brc_deflater() { brccodec::host_free(h_total); }
 };
-
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-#define HIPOK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); return BRC_E_HIP; } } while (0)
-
-template <class T> static int grow_dev(brc_deflater* h, T** p, size_t* cap, size_t want) {
-    if (want <= *cap) return BRC_OK;
-    if (*p) { HIPOK(hipFree(*p)); *p = nullptr; *cap = 0; }
-    const size_t n = want + want / 4 + 4096;
-    if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; h->err = "out of device memory"; return BRC_E_NOMEM; }
-    *cap = n;
-    return BRC_OK;
-}
-static int grow_host(brc_deflater* h, uint8_t** p, size_t* cap, size_t want) {
-    if (want <= *cap) return BRC_OK;
-    if (*p) { HIPOK(hipHostFree(*p)); *p = nullptr; *cap = 0; }
-    const size_t n = want + want / 4 + 4096;
-    if (hipHostMalloc((void**)p, n, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; h->err = "out of page-locked memory"; return BRC_E_NOMEM; }
-    *cap = n;
-    return BRC_OK;
-}
-static bool is_pinned(const void* p) {
-    hipPointerAttribute_t a; memset(&a, 0, sizeof a);
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
 
 extern "C" {
 
 const char* brc_deflater_kind(void) { return "hip-gfx950"; }
-
-void brc_deflater_destroy(brc_deflater* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_src) (void)hipFree(h->d_src);
-    if (h->d_slots) (void)hipFree(h->d_slots);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->d_sizes) (void)hipFree(h->d_sizes);
-    if (h->d_offs) (void)hipFree(h->d_offs);
-    if (h->h_src) (void)hipHostFree(h->h_src);
-    if (h->h_dst) (void)hipHostFree(h->h_dst);
-    if (h->h_total) (void)hipHostFree(h->h_total);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
-
 int brc_deflater_create(int device, brc_deflater** out) {
-    if (!out) return BRC_E_ARG;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) { (void)hipGetLastError(); return BRC_E_NODEVICE; }
-    brc_deflater* h = new (std::nothrow) brc_deflater();
-    if (!h) return BRC_E_NOMEM;
-    h->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-        hipHostMalloc((void**)&h->h_total, sizeof(uint64_t), hipHostMallocPortable) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_deflate_bgzf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Shared)) != hipSuccess) {
-        (void)hipGetLastError(); brc_deflater_destroy(h); return BRC_E_NODEVICE;     // (no kernel for this device either: nothing falls back)
-    }
-    *out = h;
+    const int rc = brccodec::create(device, (const void*)k_deflate_bgzf, sizeof(Shared), out);
+    if (rc != BRC_OK) return rc;
+    if (!((*out)->h_total = (uint64_t*)brccodec::host_alloc(sizeof(uint64_t)))) { brccodec::destroy(*out); *out = nullptr; return BRC_E_NODEVICE; }
     return BRC_OK;
 }
-
-const char* brc_deflater_last_error(const brc_deflater* h) { return h ? h->err.c_str() : ""; }
+void brc_deflater_destroy(brc_deflater* h) { brccodec::destroy(h); }
+const char* brc_deflater_last_error(const brc_deflater* h) { return brccodec::last_error(h); }
+void brc_deflater_last_timing(const brc_deflater* h, double* kernel_s, double* call_s, uint64_t* bytes_in, uint64_t* bytes_out) { brccodec::last_timing(h, kernel_s, call_s, bytes_in, bytes_out); }
+void* brc_deflate_host_alloc(size_t bytes) { return brccodec::host_alloc(bytes); }
+void brc_deflate_host_free(void* p) { brccodec::host_free(p); }
 
 size_t brc_deflate_bound(size_t src_len) { return bound(src_len); }
 const uint8_t* brc_deflate_eof_block(size_t* len) { if (len) *len = EOF_LEN; return eof_member(); }
 
-void* brc_deflate_host_alloc(size_t bytes) { void* p = nullptr; if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; }
-void brc_deflate_host_free(void* p) { if (p) (void)hipHostFree(p); }
-
-void brc_deflater_last_timing(const brc_deflater* h, double* kernel_s, double* call_s, uint64_t* bytes_in, uint64_t* bytes_out) {
-    if (!h) return;
-    if (kernel_s) *kernel_s = h->kernel_s;
-    if (call_s) *call_s = h->call_s;
-    if (bytes_in) *bytes_in = h->bytes_in;
-    if (bytes_out) *bytes_out = h->bytes_out;
-}
-
 int brc_deflate_bgzf(brc_deflater* h, const void* src_, size_t src_len, void* dst_, size_t dst_cap, size_t* dst_len, size_t* n_members_out) {
     if (!h || !dst_len || !n_members_out || (!src_ && src_len) || (!dst_ && src_len) || dst_cap < bound(src_len)) return BRC_E_ARG;
-    std::lock_guard<std::mutex> guard(h->mu);
-    const double t0 = now_s();
-    h->err.clear(); h->kernel_s = 0; h->call_s = 0; h->bytes_in = 0; h->bytes_out = 0;
+    brccodec::Call call(h);
     *dst_len = 0; *n_members_out = 0;
     const size_t n = n_members(src_len);
-    if (n == 0) { h->call_s = now_s() - t0; return BRC_OK; }
+    if (n == 0) return call.early(BRC_OK);
     if (n > 0x7fffffffu) return BRC_E_ARG;
-    const uint8_t* src = (const uint8_t*)src_; uint8_t* dst = (uint8_t*)dst_;
+    uint8_t* dst = (uint8_t*)dst_;
     HIPOK(hipSetDevice(h->device));
     int g;
-    if ((g = grow_dev(h, &h->d_src, &h->cap_src, src_len + 16)) || (g = grow_dev(h, &h->d_slots, &h->cap_slots, n * (size_t)SLOT)) ||
-        (g = grow_dev(h, &h->d_out, &h->cap_out, n * (size_t)SLOT)) || (g = grow_dev(h, &h->d_sizes, &h->cap_sizes, n)) || (g = grow_dev(h, &h->d_offs, &h->cap_offs, n + 1))) return g;
-    const uint8_t* up = src;
-    if (!is_pinned(src)) { if ((g = grow_host(h, &h->h_src, &h->hcap_src, src_len))) return g; memcpy(h->h_src, src, src_len); up = h->h_src; }
-    HIPOK(hipMemcpyAsync(h->d_src, up, src_len, hipMemcpyHostToDevice, h->stream));
+    if ((g = h->d_src.grow(h, src_len + 16)) || (g = h->d_slots.grow(h, n * (size_t)SLOT)) || (g = h->d_out.grow(h, n * (size_t)SLOT)) ||
+        (g = h->d_sizes.grow(h, n)) || (g = h->d_offs.grow(h, n + 1))) return g;
+    if ((g = brccodec::upload(h, h->d_src.p, src_, src_len))) return g;
     HIPOK(hipEventRecord(h->ev0, h->stream));
-    HIPOK(hipMemsetAsync(h->d_slots, 0, n * (size_t)SLOT, h->stream));
-    hipLaunchKernelGGL(k_deflate_bgzf, dim3((unsigned)n), dim3(LANES), sizeof(Shared), h->stream, h->d_src, (uint64_t)src_len, h->d_slots, h->d_sizes, (uint32_t)n);
-    HIPOK(hipGetLastError());
-    hipLaunchKernelGGL(k_scan_sizes, dim3(1), dim3(LANES), 0, h->stream, h->d_sizes, h->d_offs, (uint32_t)n);
-    HIPOK(hipGetLastError());
-    hipLaunchKernelGGL(k_gather, dim3((unsigned)n), dim3(LANES), 0, h->stream, h->d_slots, h->d_sizes, h->d_offs, h->d_out, (uint32_t)n);
-    HIPOK(hipGetLastError());
+    HIPOK(hipMemsetAsync(h->d_slots.p, 0, n * (size_t)SLOT, h->stream));
+    LAUNCH(k_deflate_bgzf, dim3((unsigned)n), dim3(LANES), sizeof(Shared), h->stream, h->d_src.p, (uint64_t)src_len, h->d_slots.p, h->d_sizes.p, (uint32_t)n);
+    LAUNCH(k_scan_sizes, dim3(1), dim3(LANES), 0, h->stream, h->d_sizes.p, h->d_offs.p, (uint32_t)n);
+    LAUNCH(k_gather, dim3((unsigned)n), dim3(LANES), 0, h->stream, h->d_slots.p, h->d_sizes.p, h->d_offs.p, h->d_out.p, (uint32_t)n);
     HIPOK(hipEventRecord(h->ev1, h->stream));
     // (the total decides how many bytes to fetch, so it is waited for first)
-    HIPOK(hipMemcpyAsync(h->h_total, h->d_offs + n, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPOK(hipMemcpyAsync(h->h_total, h->d_offs.p + n, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
     const size_t total = (size_t)*h->h_total;
     if (total > dst_cap || total > n * (size_t)SLOT) { h->err = "the members outgrew their bound"; return BRC_E_HIP; }      // (cannot happen: every member is at most its input + 31)
-    uint8_t* down = dst;
-    const bool dst_pinned = is_pinned(dst);
-    if (!dst_pinned) { if ((g = grow_host(h, &h->h_dst, &h->hcap_dst, total))) return g; down = h->h_dst; }
-    HIPOK(hipMemcpyAsync(down, h->d_out, total, hipMemcpyDeviceToHost, h->stream));
+    bool dst_pinned;
+    if ((g = brccodec::landing(h, dst, total, &dst_pinned))) return g;
+    HIPOK(hipMemcpyAsync(dst_pinned ? dst : h->h_dst.p, h->d_out.p, total, hipMemcpyDeviceToHost, h->stream));
     HIPOK(hipStreamSynchronize(h->stream));
-    if (!dst_pinned) memcpy(dst, h->h_dst, total);
-    float ms = 0; HIPOK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    if (!dst_pinned) memcpy(dst, h->h_dst.p, total);
+    if ((g = call.done(src_len, total))) return g;
     *dst_len = total; *n_members_out = n;
-    h->kernel_s = ms * 1e-3; h->bytes_in = src_len; h->bytes_out = total; h->call_s = now_s() - t0;
     return BRC_OK;
 }
 

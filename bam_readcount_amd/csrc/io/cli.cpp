@@ -976,18 +976,21 @@ static int make_engine(Ctx& c, int device) {
 // --brc-device-inflate: the inflater library through dlopen (nothing of it is linked: the simulator's command line is this very file).
 // A missing library, entry point or device ends the run — there is no quiet return to the host path.
 #include <dlfcn.h>
+// where a codec library is looked for: the environment's word, else next to this program
+static std::string codec_lib_path(const char* env, const char* file) {
+    if (const char* e = getenv(env)) return e;
+    char exe[PATH_MAX]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
+    const std::string path = n > 0 ? std::string(exe, (size_t)n) : std::string("bam-readcount");
+    const size_t sl = path.rfind('/');
+    return (sl == std::string::npos ? std::string(".") : path.substr(0, sl)) + "/" + file;
+}
+
 static int open_inflater(Ctx& c, int device) {
     static std::mutex mu; std::lock_guard<std::mutex> g(mu);
     static void* lib = nullptr; static std::string path;
     typedef int (*create_fn)(int, void**);
     if (!lib) {
-        if (const char* e = getenv("BRC_INFLATE_LIB")) path = e;
-        else {
-            char exe[PATH_MAX]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
-            path = n > 0 ? std::string(exe, (size_t)n) : std::string("bam-readcount");
-            const size_t sl = path.rfind('/');
-            path = (sl == std::string::npos ? std::string(".") : path.substr(0, sl)) + "/libbrc_inflate_hip.so";
-        }
+        path = codec_lib_path("BRC_INFLATE_LIB", "libbrc_inflate_hip.so");
         lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
         if (!lib) { fprintf(stderr, "bam-readcount: --brc-device-inflate: cannot load the inflater library %s: %s\n", path.c_str(), dlerror()); return 1; }
     }
@@ -1007,14 +1010,7 @@ static int open_inflater(Ctx& c, int device) {
 // --brc-bgzf-output: the deflater library through dlopen, and the sink that feeds it.  A missing library, entry point or device ends the
 // run with nothing on stdout — there is no quiet return to plain text.
 static int open_bgzf_sink(int device) {
-    std::string path;
-    if (const char* e = getenv("BRC_DEFLATE_LIB")) path = e;
-    else {
-        char exe[PATH_MAX]; const ssize_t n = readlink("/proc/self/exe", exe, sizeof exe - 1);
-        path = n > 0 ? std::string(exe, (size_t)n) : std::string("bam-readcount");
-        const size_t sl = path.rfind('/');
-        path = (sl == std::string::npos ? std::string(".") : path.substr(0, sl)) + "/libbrc_deflate_hip.so";
-    }
+    const std::string path = codec_lib_path("BRC_DEFLATE_LIB", "libbrc_deflate_hip.so");
     void* lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
     if (!lib) { fprintf(stderr, "bam-readcount: --brc-bgzf-output: cannot load the deflater library %s: %s\n", path.c_str(), dlerror()); return 1; }
     typedef int (*create_fn)(int, void**);
