@@ -2194,10 +2194,23 @@ static void* pinned_alloc(size_t n) {
 static void pinned_release(void* p) { (void)hipHostFree(p); }
 static const HostAlloc kPinned = {pinned_alloc, pinned_release};
 
+// page-locked host memory of the engine's own: an HBuf that is born with kPinned and releases itself
+template <class T>
+struct PBuf : HBuf<T> {
+    PBuf() { this->A = &kPinned; } ~PBuf() { this->destroy(); }
+    PBuf(const PBuf&) = delete; PBuf& operator=(const PBuf&) = delete;
+};
+
 static std::atomic<uint64_t> g_dev_allocs{0}, g_dev_alloc_ns{0};     // BRC_ENGINE_TIMING: (re)allocations of device buffers and the time they took (several engines allocate from their own threads)
+// a device buffer of T: sized in bytes, frees itself, is never copied.  p is what kernels and copies take; as<U>() is the same
+// memory read as another type (a Piece as the three uint4 the pileup loads it as)
+template <class T>
 struct DBuf {
-    void* p = nullptr; size_t cap = 0;
+    T* p = nullptr; size_t cap = 0;
     size_t req = 0;      // the bytes the last ensure() asked for: the extent the kernels may touch (the checked build compares addresses with it, not with the rounded-up capacity)
+    DBuf() = default; DBuf(const DBuf&) = delete; DBuf& operator=(const DBuf&) = delete;
+    ~DBuf() { if (p) (void)hipFree(p); }
+    template <class U> U* as() const { return reinterpret_cast<U*>(p); }
     hipError_t ensure(size_t bytes) {
         req = bytes;
         if (bytes <= cap) return hipSuccess;
@@ -2209,13 +2222,23 @@ struct DBuf {
         const bool regrow = p != nullptr;
         if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
         size_t want = bytes + (regrow ? bytes / 2 : bytes / 8) + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { e = hipMalloc(&p, bytes); want = bytes; }
+        hipError_t e = hipMalloc((void**)&p, want);
+        if (e != hipSuccess) { e = hipMalloc((void**)&p, bytes); want = bytes; }
         if (e == hipSuccess) cap = want;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+
+// a stream / an event of the engine's: destroyed with its owner, handed to the runtime as the plain handle
+template <class H, hipError_t (*DESTROY)(H)>
+struct Owned {
+    H h = nullptr;
+    Owned() = default; Owned(const Owned&) = delete; Owned& operator=(const Owned&) = delete;
+    ~Owned() { if (h) (void)DESTROY(h); }
+    operator H() const { return h; }
+};
+typedef Owned<hipStream_t, hipStreamDestroy> Stream;
+typedef Owned<hipEvent_t, hipEventDestroy> Event;
 
 enum { T_ANNOTATE = 0, T_SCAN_ENDS, T_TILES, T_PILEUP, T_COUNT, T_INDEL_SCAN, T_INDEL_FILL, T_INDEL_REDUCE, T_N };
 static const char* kKernelNames[BRC_NKERNEL] = {"k_annotate", "k_scan_ends", "k_tiles", "k_pileup", "k_xev_fold+finalize",
@@ -2223,37 +2246,37 @@ static const char* kKernelNames[BRC_NKERNEL] = {"k_annotate", "k_scan_ends", "k_
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) { return hip_fail(_e, #x); } } while (0)
 
+// Never called.  The layout of the device object (capi.kernel_object_hash, which the committed counter passes are tied to) follows the
+// order in which the host code first names each kernel template instantiation, so that order is fixed here, once, in front of every
+// launch: the launch functions of HipBackend can then be written and ordered as reads best.  A new instantiation goes to the list's end.
+[[maybe_unused]] static void pin_instantiation_order() {
+    const void* const k[] = {(const void*)k_annotate_groups<true, 16>, (const void*)k_annotate_groups<true, 12>, (const void*)k_annotate_groups<false, 16>, (const void*)k_annotate_groups<false, 12>,
+        (const void*)k_annotate_wave<16, AW_MCAP, 4>, (const void*)k_annotate_wave<12, AW_MCAP, 4>, (const void*)k_annotate_wave<16, AW_MCAP_BIG, 1>, (const void*)k_annotate_wave<12, AW_MCAP_BIG, 1>,
+        (const void*)k_annotate_wave<16, AW_MCAP_EQX, 4, true>, (const void*)k_annotate_wave<12, AW_MCAP_EQX, 4, true>, (const void*)k_annotate_wave<16, AW_MCAP_EQX_BIG, 1, true>, (const void*)k_annotate_wave<12, AW_MCAP_EQX_BIG, 1, true>,
+        (const void*)k_annotate_wave<16, AW_MCAP_HUGE, 1>, (const void*)k_annotate_wave<12, AW_MCAP_HUGE, 1>, (const void*)k_annotate_cursor<16>, (const void*)k_annotate_cursor<12>,
+        (const void*)k_scan_reduce<OpSumU32>, (const void*)k_scan_aggregates<OpSumU32>, (const void*)k_scan_apply<OpSumU32, false>, (const void*)k_scan_aggregates<OpMaxU64>, (const void*)k_compact_tiles<true>, (const void*)k_compact_tiles<false>,
+        (const void*)k_pileup2<true, 16>, (const void*)k_pileup2<true, 12>, (const void*)k_pileup2<false, 16>, (const void*)k_pileup2<false, 12>};
+    (void)k;
+}
+
 class HipBackend : public Backend {
-    std::string err;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    // one set of timing events per pass in flight: brc_compute uses set 0, brc_compute_n a ring of them (passes queued back to
-    // back record into sets of their own, read after the one wait at the end of a batch)
-    enum { EV_RING = 32 };
-    struct EvSet { hipEvent_t evt[T_N + 1]; hipEvent_t ev_indel[4]; };
-    std::vector<EvSet> evsets;
-    hipEvent_t* evt = nullptr;           // the current pass's sets (point into evsets)
-    bool have_events = false;
+    // Members release themselves, in the reverse of the order they are declared in, and the order matters: the device buffers go first
+    // (hipFree waits for the device, and that wait is what makes the next step safe), then the page-locked memory (which the text
+    // download on stream2 may still be writing), then the events and the streams.  Hence the groups below: plain state, streams,
+    // events, page-locked buffers, device buffers.  A new buffer is one typed declaration in its group and nothing else.
+    std::string err; int device = 0;
     DevCfg c; DevIn in;
     int64_t ntiles = 0; uint64_t n_indel_cap = 0;
     std::vector<int64_t> lib_base;      // first piece of every library's stream (Lp + 1 entries)
-    // device buffers
-    DBuf d_pos, d_flag, d_mapq, d_lib, d_lq, d_nc, d_co, d_so, d_qo, d_nm, d_sm, d_tags, d_cigar, d_seq, d_qual, d_ref, d_refcode;
-    std::vector<uint16_t> h_wanted; bool has_wanted = false; DBuf d_wanted; std::vector<uint32_t> h_tilelist; DBuf d_tilelist;      // brc_region_windows (kept alive for the asynchronous copy)
-    HBuf<Staged::WidePair> h_wpairs; unsigned wide_slices = 1;      // (page-locked: the list is every read of a run with HiFi qualities)
-    DBuf d_wpairs;
-    DBuf d_bq, d_bqw, d_bqrow, d_pieceoff, d_pieces, d_rare, d_keyreach, d_libbase, d_reads, d_agg, d_rng, d_ncol, d_depth, d_slotid, d_si, d_sf, d_xev, d_xevc, d_xevn, d_unavail, d_cnt, d_cursor, d_ev, d_evraw, d_ievoff, d_iout, d_ctr, d_tilectr, d_part, d_wavelist, d_nc_k1;
-    DBuf d_tlen, d_toff, d_text, d_tctx, d_total64, d_lastproc;
-    DBuf d_xcnt, d_xend, d_xidx, d_xagg;   // the third-allele fold: events per (tile, library) bucket, the buckets' ends, the events' indices by bucket, the folded records
-    // device-side text, downloaded (pinned) on its own stream into one of two host buffers
-    HBuf<char> h_text[2]; HBuf<uint32_t> h_toff[2]; HBuf<uint32_t> h_total;
-    hipStream_t stream2 = nullptr; hipEvent_t ev_text[2] = {nullptr, nullptr}, ev_lines = nullptr;
-    hipStream_t stream3 = nullptr; hipEvent_t* ev_indel = nullptr; DBuf d_agg2;   // the indel side path's stream
+    std::vector<uint16_t> h_wanted; bool has_wanted = false; std::vector<uint32_t> h_tilelist;      // brc_region_windows (kept alive for the asynchronous copy)
+    unsigned wide_slices = 1;
     bool text_started[2] = {false, false}; uint64_t text_total[2] = {0, 0}; int64_t text_n[2] = {0, 0}; int text_slot = 0;
+    std::mutex text_mu;                  // reserve_text may run on another thread while the first region is staged
     Planes pl_last;                      // the planes of the last compute
     // tile compaction (k_compact_tiles): on for regions whose reads average more than COMPACT_PIECES_PER_READ pieces
     enum { COMPACT_PIECES_PER_READ = 12 };
     bool compact_on = false; uint64_t compact_total = 0; bool compact_sized = false;
+    struct { const uint4* pieces; const PieceRare* rare; const uint2* rng; } kp = {nullptr, nullptr, nullptr};   // what k_pileup2 reads its records and ranges from: K1's stream, or the compacted one
     bool wave_on = false;                      // this region's reads with more than two M operators go to k_annotate_wave
     bool wave_big = false;                     // ... and some may have more than AW_MCAP M operators (a read with more than AW_MCAP operators exists)
     enum { WAVE_FORM_BLOCKS = 768,             // its fixed grid: 3 blocks of 4 waves per CU (48 KB of LDS each)
@@ -2263,22 +2286,44 @@ class HipBackend : public Backend {
     bool wave_eqx = false; uint32_t s_max_ncigar = 0;   // reads with = / X operators exist: the EQX instantiations are launched too
     bool cursor_on = false;                    // a read with an empty M / = / X operator was staged: k_pick_wave lists such reads for k_annotate_cursor
     unsigned long long h_steps[3] = {0, 0, 0};   // piece-steps of the last pass: what the tile ranges hold / what k_pileup2 walked (brc_region_piece_steps)
-    DBuf d_ccnt, d_coff, d_cpieces, d_crare, d_crng, d_ctot;
-    // host result buffers (pinned)
-    HBuf<uint32_t> h_ncol, h_depth, h_slotid, h_si, h_unavail; HBuf<float> h_sf; HBuf<IndelOut> h_iout; HBuf<XAgg> h_xagg; HBuf<uint32_t> h_lastproc[2];
-    std::vector<XAgg> xagg_compact;
-    size_t xev_cap = 0;                  // entries per sub-list
-    enum { XEV_SHARDS = 1024 };
-    std::vector<IndelOut> iout_compact;
-    Counters h_ctr;
-    bool computed = false;
+    std::vector<XAgg> xagg_compact; std::vector<IndelOut> iout_compact;
+    enum { XEV_SHARDS = 1024 }; size_t xev_cap = 0;      // the third-allele lists: sub-lists, entries per sub-list
+    Counters h_ctr; bool computed = false;
+    bool lists_enqueued = false, lists_host = false;     // the two lists of the last compute are on their way to h_xagg / h_iout; xagg_compact / iout_compact hold them
+    Stream stream, stream2;              // the engine's; the text download's (pinned, into one of two host buffers)
+    // one set of timing events per pass in flight: brc_compute uses set 0, brc_compute_n a ring of them (passes queued back to
+    // back record into sets of their own, read after the one wait at the end of a batch)
+    enum { EV_RING = 32 };
+    struct EvSet { Event evt[T_N + 1], ev_indel[4]; };
+    EvSet evsets[EV_RING]; size_t n_evsets = 0;
+    Event* evt = nullptr; Event* ev_indel = nullptr;           // the current pass's sets (point into evsets)
+    Event ev_text[2], ev_lines;
+    // page-locked host buffers
+    PBuf<Staged::WidePair> h_wpairs; PBuf<char> h_text[2]; PBuf<uint32_t> h_toff[2], h_total, h_lastproc[2];      // (h_wpairs: every read of a run with HiFi qualities)
+    struct HostSet { PBuf<uint32_t> ncol, depth, slotid, si, unavail; PBuf<float> sf; } h_pl, w_pl;      // the result planes: whole (brc_fetch) / a window's (brc_fetch_window)
+    PBuf<IndelOut> h_iout; PBuf<XAgg> h_xagg;
+    // device buffers: the staged reads
+    DBuf<int32_t> d_pos, d_lq, d_nm, d_sm; DBuf<uint16_t> d_flag; DBuf<uint8_t> d_mapq, d_tags, d_seq, d_qual; DBuf<int16_t> d_lib;
+    DBuf<uint32_t> d_nc, d_cigar, d_pieceoff, d_ievoff; DBuf<uint64_t> d_co, d_so, d_qo, d_bqrow; DBuf<char> d_ref; DBuf<uint8_t> d_refcode;
+    DBuf<uint16_t> d_wanted; DBuf<uint32_t> d_tilelist; DBuf<uint2> d_wpairs; DBuf<int64_t> d_libbase;
+    // ... what the annotators write: event bytes, wide words, pieces, tile ranges
+    DBuf<uint8_t> d_bq; DBuf<uint16_t> d_bqw; DBuf<Piece> d_pieces; DBuf<PieceRare> d_rare; DBuf<int2> d_keyreach; DBuf<DRead> d_reads;
+    DBuf<uint32_t> d_wavelist, d_nc_k1; DBuf<unsigned long long> d_agg; DBuf<uint2> d_rng;
+    DBuf<uint32_t> d_ccnt, d_coff; DBuf<Piece> d_cpieces; DBuf<PieceRare> d_crare; DBuf<uint2> d_crng; DBuf<unsigned long long> d_ctot;   // (the compacted stream)
+    // ... the planes, the counters
+    DBuf<uint32_t> d_ncol, d_depth, d_slotid, d_si, d_unavail; DBuf<float> d_sf; DBuf<uint4> d_tilectr; DBuf<unsigned long long> d_part; DBuf<Counters> d_ctr;
+    // ... the third-allele lists and their fold: events per (tile, library) bucket, the buckets' ends, the events' indices by bucket, the folded records
+    DBuf<XEv> d_xev, d_xevc; DBuf<uint32_t> d_xevn, d_xcnt, d_xend, d_xidx; DBuf<XAgg> d_xagg;
+    // ... the indel path; the device-side text
+    DBuf<uint32_t> d_cnt, d_cursor; DBuf<IndelEv> d_ev, d_evraw; DBuf<IndelOut> d_iout;
+    DBuf<uint32_t> d_tlen, d_toff, d_lastproc; DBuf<char> d_text, d_tctx; DBuf<unsigned long long> d_total64;
 #ifdef BRC_CHECKED
     // the bounds-checked build: extents of every buffer K1 and k_pileup2 address (what the host asked for), uploaded in front of
     // every pass; the fault record is read back behind it (finish_passes)
-    DBuf d_chk; ChkState h_chk;
+    DBuf<ChkState> d_chk; ChkState h_chk;
     void chk_fill() {
         memset(&h_chk, 0, sizeof h_chk);
-        auto set = [&](int b, const DBuf& d) { h_chk.ext[b].lo = (uint64_t)d.p; h_chk.ext[b].hi = (uint64_t)d.p + d.req; };
+        auto set = [&](int b, const auto& d) { h_chk.ext[b].lo = (uint64_t)d.p; h_chk.ext[b].hi = (uint64_t)d.p + d.req; };
         set(CB_CIGAR, d_cigar); set(CB_SEQ, d_seq); set(CB_QUAL, d_qual); set(CB_REFCODE, d_refcode); set(CB_EB, d_bq); set(CB_BQW, d_bqw);
         set(CB_PIECES, d_pieces); set(CB_RARE, d_rare); set(CB_KEYREACH, d_keyreach); set(CB_READS, d_reads); set(CB_EVRAW, d_evraw); set(CB_CNT, d_cnt);
         set(CB_WANTED, d_wanted); set(CB_RNG, d_rng); set(CB_UNAVAIL, d_unavail); set(CB_TILELIST, d_tilelist); set(CB_NCOL, d_ncol); set(CB_DEPTH, d_depth);
@@ -2311,6 +2356,14 @@ class HipBackend : public Backend {
         err = b;
         return e == hipErrorOutOfMemory ? BRC_E_NOMEM : BRC_E_HIP;
     }
+    // the indel path runs in this region's passes
+    bool indels_active() const { return n_indel_cap > 0 && c.P > 0 && c.n_reads > 0; }
+    // the third-allele lists at their current capacity (upload; grown behind a pass that overflowed one)
+    int ensure_xev_lists() {
+        const size_t n = (size_t)XEV_SHARDS * xev_cap + 1;
+        HIPCHK(d_xev.ensure(n * sizeof(XEv))); HIPCHK(d_xevc.ensure(n * sizeof(XEv))); HIPCHK(d_xidx.ensure(n * 4)); HIPCHK(d_xagg.ensure(n * sizeof(XAgg)));
+        return BRC_OK;
+    }
 
   public:
     int init(int dev) {
@@ -2319,10 +2372,9 @@ class HipBackend : public Backend {
         if (dev < 0 || dev >= n) { err = "device ordinal out of range"; return BRC_E_NODEVICE; }
         device = dev;
         HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&stream.h, hipStreamNonBlocking));
         { const int rc0 = ensure_evsets(1); if (rc0) return rc0; }
-        HIPCHK(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&stream3, hipStreamNonBlocking));
+        HIPCHK(hipStreamCreateWithFlags(&stream2.h, hipStreamNonBlocking));
         {
             uint32_t* d_bad = nullptr; uint32_t bad = 0;
             HIPCHK(hipMalloc(&d_bad, sizeof(uint32_t)));
@@ -2333,59 +2385,37 @@ class HipBackend : public Backend {
             (void)hipFree(d_bad);
             if (bad) { err = "this device's reciprocal does not give correctly rounded small-integer quotients (div_small self-check failed)"; return BRC_E_HIP; }
         }
-        for (int i = 0; i < 2; ++i) { HIPCHK(hipEventCreateWithFlags(&ev_text[i], hipEventDisableTiming)); h_text[i].A = &kPinned; h_toff[i].A = &kPinned; }
-        HIPCHK(hipEventCreateWithFlags(&ev_lines, hipEventDisableTiming));
-        h_total.A = &kPinned;
-        h_ncol.A = h_depth.A = h_slotid.A = h_si.A = h_unavail.A = &kPinned; h_sf.A = &kPinned; h_iout.A = &kPinned; h_xagg.A = &kPinned; h_wpairs.A = &kPinned; h_lastproc[0].A = h_lastproc[1].A = &kPinned;
+        for (Event& e : ev_text) HIPCHK(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ev_lines.h, hipEventDisableTiming));
         return BRC_OK;
     }
-    ~HipBackend() override {
+    ~HipBackend() override {      // (the members follow, last declared first: see the head of the class)
         (void)hipSetDevice(device);
         if (getenv("BRC_ENGINE_TIMING")) fprintf(stderr, "device buffers: %llu (re)allocations, %.3f s\n", (unsigned long long)g_dev_allocs.load(), (double)g_dev_alloc_ns.load() * 1e-9);
-        DBuf* all[] = {&d_pos, &d_flag, &d_mapq, &d_lib, &d_lq, &d_nc, &d_co, &d_so, &d_qo, &d_nm, &d_sm, &d_tags, &d_cigar, &d_seq, &d_qual,
-                       &d_ref, &d_refcode, &d_bq, &d_bqw, &d_bqrow, &d_pieceoff, &d_pieces, &d_rare, &d_keyreach, &d_libbase, &d_reads, &d_agg, &d_rng, &d_ncol, &d_depth, &d_slotid, &d_si, &d_sf, &d_xev, &d_xevc, &d_xevn, &d_unavail, &d_cnt,
-                       &d_cursor, &d_ev, &d_evraw, &d_ievoff, &d_iout, &d_ctr, &d_tilectr, &d_part, &d_tlen, &d_toff, &d_text, &d_tctx, &d_total64, &d_lastproc, &d_xcnt, &d_xend, &d_xidx, &d_xagg, &d_wanted, &d_tilelist, &d_wavelist, &d_nc_k1, &d_wpairs};
-        for (DBuf* b : all) b->release();
-        d_ccnt.release(); d_coff.release(); d_cpieces.release(); d_crare.release(); d_crng.release(); d_ctot.release();
-#ifdef BRC_CHECKED
-        d_chk.release();
-#endif
-        for (int i = 0; i < 2; ++i) { h_text[i].destroy(); h_toff[i].destroy(); if (ev_text[i]) (void)hipEventDestroy(ev_text[i]); }
-        h_total.destroy();
-        if (ev_lines) (void)hipEventDestroy(ev_lines);
-        if (stream2) (void)hipStreamDestroy(stream2);
-        if (stream3) (void)hipStreamDestroy(stream3);
-        d_agg2.release();
-        h_ncol.destroy(); h_depth.destroy(); h_slotid.destroy(); h_si.destroy(); h_unavail.destroy(); h_sf.destroy(); h_iout.destroy(); h_xagg.destroy(); h_wpairs.destroy(); h_lastproc[0].destroy(); h_lastproc[1].destroy();
-        if (w_init) { w_ncol.destroy(); w_depth.destroy(); w_slotid.destroy(); w_si.destroy(); w_unavail.destroy(); w_sf.destroy(); }
-        for (EvSet& es : evsets) { for (int i = 0; i <= T_N; ++i) if (es.evt[i]) (void)hipEventDestroy(es.evt[i]); for (int i = 0; i < 4; ++i) if (es.ev_indel[i]) (void)hipEventDestroy(es.ev_indel[i]); }
-        if (stream) (void)hipStreamDestroy(stream);
     }
     int ensure_evsets(size_t n) {
-        while (evsets.size() < n) {
-            EvSet es; memset(&es, 0, sizeof es);
-            evsets.push_back(es);
-            for (int i = 0; i <= T_N; ++i) HIPCHK(hipEventCreate(&evsets.back().evt[i]));
-            for (int i = 0; i < 4; ++i) HIPCHK(hipEventCreate(&evsets.back().ev_indel[i]));
+        for (; n_evsets < n; ++n_evsets) {      // (a set counts once all its events exist)
+            for (Event& e : evsets[n_evsets].evt) if (!e.h) HIPCHK(hipEventCreate(&e.h));
+            for (Event& e : evsets[n_evsets].ev_indel) if (!e.h) HIPCHK(hipEventCreate(&e.h));
         }
-        evt = evsets[0].evt; ev_indel = evsets[0].ev_indel; have_events = true;
+        evt = evsets[0].evt; ev_indel = evsets[0].ev_indel;
         return BRC_OK;
     }
     const HostAlloc* host_alloc() override { return &kPinned; }
     const char* last_error() const override { return err.c_str(); }
 
     template <class T>
-    int up(DBuf& d, const HBuf<T>& h, size_t n) {
+    int up(DBuf<T>& d, const HBuf<T>& h, size_t n) {
         HIPCHK(d.ensure((n + 16) * sizeof(T)));
         if (n) HIPCHK(hipMemcpyAsync(d.p, h.p, n * sizeof(T), hipMemcpyHostToDevice, stream));
         return BRC_OK;
     }
 
     // SEQ / QUAL: from the staging copy, or — brc_push_reads_pinned — segment by segment from the caller's page-locked buffers
-    int up_arena(DBuf& d, const HBuf<uint8_t>& h, const std::vector<Staged::Seg>& segs, uint64_t total) {
+    int up_arena(DBuf<uint8_t>& d, const HBuf<uint8_t>& h, const std::vector<Staged::Seg>& segs, uint64_t total) {
         if (segs.empty()) return up(d, h, h.n);
         HIPCHK(d.ensure((size_t)total + 16));
-        for (const Staged::Seg& g : segs) if (g.n) HIPCHK(hipMemcpyAsync((uint8_t*)d.p + g.off, g.p, (size_t)g.n, hipMemcpyHostToDevice, stream));
+        for (const Staged::Seg& g : segs) if (g.n) HIPCHK(hipMemcpyAsync(d.p + g.off, g.p, (size_t)g.n, hipMemcpyHostToDevice, stream));
         return BRC_OK;
     }
     bool adopts_arenas() const override { return true; }
@@ -2427,16 +2457,13 @@ class HipBackend : public Backend {
         HIPCHK(d_ref.ensure(rl + 16));
         HIPCHK(d_refcode.ensure(rl + 2 * REFCODE_PAD + 16));
         if (rl) HIPCHK(hipMemcpyAsync(d_ref.p, g.ref + g.ref_lo, rl, hipMemcpyHostToDevice, stream));
-        in.pos = (const int32_t*)d_pos.p; in.flag = (const uint16_t*)d_flag.p; in.mapq = (const uint8_t*)d_mapq.p; in.lib = (const int16_t*)d_lib.p;
-        in.l_qseq = (const int32_t*)d_lq.p; in.n_cigar = (const uint32_t*)d_nc.p; in.cig_off = (const uint64_t*)d_co.p;
-        in.seq_off = (const uint64_t*)d_so.p; in.qual_off = (const uint64_t*)d_qo.p; in.nm = (const int32_t*)d_nm.p; in.sm = (const int32_t*)d_sm.p;
-        in.tags = (const uint8_t*)d_tags.p; in.cigar = (const uint32_t*)d_cigar.p; in.seq4 = (const uint8_t*)d_seq.p; in.qual = (const uint8_t*)d_qual.p;
-        in.ref = (const char*)d_ref.p;
+        in.pos = d_pos.p; in.flag = d_flag.p; in.mapq = d_mapq.p; in.lib = d_lib.p; in.l_qseq = d_lq.p; in.n_cigar = d_nc.p; in.cig_off = d_co.p;
+        in.seq_off = d_so.p; in.qual_off = d_qo.p; in.nm = d_nm.p; in.sm = d_sm.p; in.tags = d_tags.p; in.cigar = d_cigar.p; in.seq4 = d_seq.p; in.qual = d_qual.p;
+        in.ref = d_ref.p;
         // event-byte stream, padded on both sides: a staged window starts up to 79 elements before / ends after a row
         // (the wide stream — full words of the few 8-base groups with an escape byte — has rows for the reads the host found such
         // a base in: DevIn.bqw)
-        enum { BQ_PAD = EB_PAD_FRONT };
-        HIPCHK(d_bq.ensure(s.bq_elems + BQ_PAD + EB_PAD_BACK + (size_t)std::max<int32_t>(s.max_lqseq, 0)));     // (brc_core.h: stage_window_start — a staged window ends at most that far past the stream)
+        HIPCHK(d_bq.ensure(s.bq_elems + EB_PAD_FRONT + EB_PAD_BACK + (size_t)std::max<int32_t>(s.max_lqseq, 0)));     // (brc_core.h: stage_window_start — a staged window ends at most that far past the stream)
         {   // the sparse wide stream: [table: one u32 per 16 elements of the byte stream][rows of the wide reads] (brc_core.h: DevIn.bqw)
             if (s.bq_elems >> 34) { err = "region too large: 2^34 bases and more"; return BRC_E_LIMIT; }      // (k_pileup2 reaches a table entry through a 32-bit byte offset)
             const size_t tab_bytes = ((((size_t)(s.bq_elems >> 4) + 2) * 4) + 255) & ~(size_t)255;
@@ -2449,7 +2476,7 @@ class HipBackend : public Backend {
             }
             if ((tab_bytes / 32 + (wq_elems >> 4)) >> 32) { err = "region too large: 2^36 bases of reads with escape bases"; return BRC_E_LIMIT; }
             HIPCHK(d_bqw.ensure(tab_bytes + ((size_t)wq_elems + 16) * sizeof(uint16_t)));
-            in.bqw = (const uint16_t*)d_bqw.p;
+            in.bqw = d_bqw.p;
 #ifdef BRC_CHECKED
             HIPCHK(hipMemsetAsync(d_bqw.p, 0xff, tab_bytes, stream));        // (an entry nobody set points far outside the stream)
 #endif
@@ -2458,9 +2485,9 @@ class HipBackend : public Backend {
                 HIPCHK(hipMemcpyAsync(d_wpairs.p, h_wpairs.p, h_wpairs.n * sizeof(Staged::WidePair), hipMemcpyHostToDevice, stream));
             }
         }
-        in.eb = (const uint8_t*)d_bq.p + BQ_PAD;
+        in.eb = d_bq.p + EB_PAD_FRONT;
         if ((rc = up(d_bqrow, s.bq_row, n)) || (rc = up(d_pieceoff, s.piece_off, n))) return rc;
-        in.bq_row = (const uint64_t*)d_bqrow.p;
+        in.bq_row = d_bqrow.p;
         in.rcp = nullptr;
         const size_t np = (size_t)c.n_pieces;
         HIPCHK(d_pieces.ensure((np + 4) * sizeof(Piece))); HIPCHK(d_rare.ensure((np + 2) * sizeof(PieceRare)));      // (the read loop requests records up to two past the last)
@@ -2494,7 +2521,7 @@ class HipBackend : public Backend {
         if (n_indel_cap && ((uint64_t)c.P * (uint64_t)c.Lp >= 0xffffffffull || n_indel_cap >= 0xfffffff0ull)) { err = "region too large: (positions x libraries) and the indel operators must stay below 2^32"; return BRC_E_ARG; }
         const size_t nagg = std::max<size_t>(std::max<size_t>((std::max<size_t>(np, P * Lp) + SCAN_CHUNK - 1) / SCAN_CHUNK, (np + TR_CHUNK - 1) / TR_CHUNK), 1);
         HIPCHK(d_reads.ensure((n + 1) * sizeof(DRead)));
-        HIPCHK(d_agg.ensure(nagg * 8 + 16)); HIPCHK(d_agg2.ensure(nagg * 4 + 16)); HIPCHK(d_rng.ensure(((size_t)ntiles * Lp + 1) * sizeof(uint2)));
+        HIPCHK(d_agg.ensure(nagg * 8 + 16)); HIPCHK(d_rng.ensure(((size_t)ntiles * Lp + 1) * sizeof(uint2)));
         HIPCHK(d_ncol.ensure(Lp * P * 4 + 16)); HIPCHK(d_depth.ensure(Lp * P * 4 + 16)); HIPCHK(d_unavail.ensure(P * 4 + 16));
         HIPCHK(d_slotid.ensure(Lp * P * 4 + 16)); HIPCHK(d_si.ensure(Lp * 2 * NI * P * 4 + 16)); HIPCHK(d_sf.ensure(Lp * 2 * NF * P * 4 + 16));
         // third-allele lists: XEV_SHARDS sub-lists; about one piece in 25 leaves an event at 30-50x, capacity for twice that,
@@ -2504,19 +2531,18 @@ class HipBackend : public Backend {
             const size_t want = xc ? (size_t)std::max(atoi(xc), 1) : std::max<size_t>(256, np / 8 / XEV_SHARDS);
             if (want > xev_cap) xev_cap = want;
         }
-        HIPCHK(d_xev.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * sizeof(XEv))); HIPCHK(d_xevc.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * sizeof(XEv)));
+        if ((rc = ensure_xev_lists())) return rc;
         HIPCHK(d_xevn.ensure((size_t)XEV_SHARDS * XEV_CTR_STRIDE * 4));
-        HIPCHK(d_xidx.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * 4)); HIPCHK(d_xagg.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * sizeof(XAgg)));
         HIPCHK(d_xcnt.ensure(((size_t)ntiles * Lp + 2) * 4)); HIPCHK(d_xend.ensure(((size_t)ntiles * Lp + 2) * 4));
         HIPCHK(d_part.ensure(4096 * 5 * sizeof(unsigned long long)));
         HIPCHK(d_ctr.ensure(sizeof(Counters))); HIPCHK(d_tilectr.ensure(((size_t)ntiles * Lp + 1) * sizeof(uint4)));
         in.iev_off = nullptr;
         if (n_indel_cap) {
-            // indel side path: raw events (one slot per I / D / P operator, at host-computed per-read offsets), their counts
+            // indel path: raw events (one slot per I / D / P operator, at host-computed per-read offsets), their counts
             // per (16 or 64 positions, library) bucket, the bucketed events and the reduced alleles
             const size_t nbk = (size_t)indel_buckets(c);
             if ((rc = up(d_ievoff, s.iev_off, n))) return rc;
-            in.iev_off = (const uint32_t*)d_ievoff.p;
+            in.iev_off = d_ievoff.p;
             HIPCHK(d_cnt.ensure(nbk * 4 + 16)); HIPCHK(d_cursor.ensure(nbk * 4 + 16)); HIPCHK(d_evraw.ensure((n_indel_cap + 1) * sizeof(IndelEv)));
             HIPCHK(d_ev.ensure((n_indel_cap + 1) * sizeof(IndelEv))); HIPCHK(d_iout.ensure((n_indel_cap + 1) * sizeof(IndelOut)));
         }
@@ -2531,240 +2557,231 @@ class HipBackend : public Backend {
         return BRC_OK;
     }
 
+    // ---- launches: one function per kernel family, each kernel's argument list written once.  A new kernel is a launch function here
+    // and a call in its stage below (a new template instantiation also a line in pin_instantiation_order).
+    // the instantiation for this region's width of the narrow packed fields (choose_pack): SH = 16 or 12
+    template <class K> K by_pack(K k16, K k12) const { return c.pack_shift == 16 ? k16 : k12; }
+    // what the annotators share: the event bytes they write (in.eb), the raw indel events (none: no indel path), the announced windows (none: all)
+    uint8_t* eb_out() const { return d_bq.p + EB_PAD_FRONT; }
+    IndelEv* evraw() const { return indels_active() ? d_evraw.p : nullptr; }
+    const uint16_t* wanted() const { return has_wanted ? d_wanted.p : nullptr; }
+    const uint8_t* refcode() const { return d_refcode.p + REFCODE_PAD; }
+
+    // K1: one instantiation per (row layout, width of the narrow packed fields)
+    void launch_annotate_groups(const DevIn& in_k1) {
+        const auto k = c.Lp == 1 ? by_pack(k_annotate_groups<true, 16>, k_annotate_groups<true, 12>) : by_pack(k_annotate_groups<false, 16>, k_annotate_groups<false, 12>);
+        hipLaunchKernelGGL(k, dim3((unsigned)((c.n_reads + 255) / 256)), dim3(256), 0, stream, c, in_k1, d_reads.p, d_pieceoff.p, d_pieces.p, d_rare.p, d_keyreach.p,
+                           eb_out(), evraw(), d_cnt.p, in.cigar, in.qual, in.seq4, refcode(), wanted());
+    }
+    // the wave form: `grid` workgroups of WAVES waves take the reads of `list` (read in steps of `step`, `count` of them: a number that stays on the device) round robin
+    template <int MCAP, int WAVES, bool EQX = false>
+    void launch_annotate_wave(unsigned grid, const uint32_t* list, int step, const unsigned int* count) {
+        hipLaunchKernelGGL(by_pack(k_annotate_wave<16, MCAP, WAVES, EQX>, k_annotate_wave<12, MCAP, WAVES, EQX>), dim3(grid), dim3(WAVES * 64), 0, stream, c, in, list, step, count,
+                           d_reads.p, d_pieceoff.p, d_pieces.p, d_rare.p, d_keyreach.p, eb_out(), evraw(), d_cnt.p, refcode(), wanted());
+    }
+    void launch_annotate_cursor() {
+        hipLaunchKernelGGL(by_pack(k_annotate_cursor<16>, k_annotate_cursor<12>), dim3((unsigned)std::min<int64_t>((c.n_reads + 63) / 64, 1024)), dim3(64), 0, stream, c, in,
+                           d_wavelist.p + (2 * (size_t)c.n_reads + 32), &d_ctr.p->n_literal, d_reads.p, d_pieceoff.p, d_pieces.p, d_rare.p, d_keyreach.p, eb_out(), evraw(), d_cnt.p, wanted());
+    }
+    // exclusive or inclusive scan of n elements (block aggregates in d_agg)
     template <class Op, bool INCL>
-    int scan(const typename Op::T* src, typename Op::T* dst, int64_t n) { return scan_on<Op, INCL>(src, dst, n, stream, d_agg); }
-    // (the indel side path scans on its own stream with its own block-aggregate scratch)
-    template <class Op, bool INCL>
-    int scan_on(const typename Op::T* src, typename Op::T* dst, int64_t n, hipStream_t st, DBuf& scratch) {
+    int scan(const typename Op::T* src, typename Op::T* dst, int64_t n) {
         if (n <= 0) return BRC_OK;
         const int64_t nb = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
-        typename Op::T* agg = (typename Op::T*)scratch.p;
-        hipLaunchKernelGGL((k_scan_reduce<Op>), dim3((unsigned)nb), dim3(SCAN_T), 0, st, src, n, agg);
-        hipLaunchKernelGGL((k_scan_aggregates<Op>), dim3(1), dim3(1024), 0, st, agg, nb);
-        hipLaunchKernelGGL((k_scan_apply<Op, INCL>), dim3((unsigned)nb), dim3(SCAN_T), 0, st, src, dst, n, (const typename Op::T*)agg);
+        typename Op::T* agg = d_agg.as<typename Op::T>();
+        hipLaunchKernelGGL((k_scan_reduce<Op>), dim3((unsigned)nb), dim3(SCAN_T), 0, stream, src, n, agg);
+        hipLaunchKernelGGL((k_scan_aggregates<Op>), dim3(1), dim3(1024), 0, stream, agg, nb);
+        hipLaunchKernelGGL((k_scan_apply<Op, INCL>), dim3((unsigned)nb), dim3(SCAN_T), 0, stream, src, dst, n, agg);
         HIPCHK(hipGetLastError());
         return BRC_OK;
     }
+    // COUNT: the live pieces of every (tile, library) -> d_ccnt; else: the copy behind the scanned offsets
+    template <bool COUNT>
+    void launch_compact_tiles() {
+        hipLaunchKernelGGL((k_compact_tiles<COUNT>), dim3((unsigned)((ntiles + 3) / 4), (unsigned)c.Lp), dim3(256), 0, stream, c, d_pieces.as<const uint4>(), d_rare.p, d_rng.p, ntiles, d_ccnt.p,
+                           COUNT ? nullptr : d_coff.p, COUNT ? nullptr : d_cpieces.as<uint4>(), COUNT ? nullptr : d_crare.p, COUNT ? nullptr : d_crng.p, d_ctot.p);
+    }
+    // k_pileup2: one instantiation per (announced windows or all tiles, width of the narrow packed fields); reads kp.  The pileup stage of a pass is this one launch
+    void stage_pileup() {
+        const int64_t n_listed = (int64_t)h_tilelist.size();
+        if (ntiles <= 0 || (has_wanted && n_listed == 0)) return;
+        unsigned nwg = (unsigned)(((has_wanted ? n_listed : ntiles) + PILEUP_WAVES - 1) / PILEUP_WAVES);
+        nwg = (nwg + 7u) & ~7u;
+        // profiling knob: unused dynamic LDS lowers the number of resident waves (occupancy sweeps)
+#ifdef BRC_EXP_KNOBS
+        static const unsigned dyn_lds = getenv("BRC_PILEUP_LDS_PAD") ? (unsigned)atoi(getenv("BRC_PILEUP_LDS_PAD")) : 0u;
+#else
+        const unsigned dyn_lds = 0u;
+#endif
+        const auto k = has_wanted ? by_pack(k_pileup2<true, 16>, k_pileup2<true, 12>) : by_pack(k_pileup2<false, 16>, k_pileup2<false, 12>);
+        hipLaunchKernelGGL(k, dim3(nwg, (unsigned)c.Lp), dim3(PILEUP_WAVES * 64), dyn_lds, stream, c, in, kp.pieces, kp.rare, kp.rng, ntiles, pl_last, d_tilectr.p, in.eb, in.bqw, d_unavail.p,
+                           refcode(), d_wanted.p, d_tilelist.p, n_listed);
+    }
 
-    // One pass of the whole pipeline, queued on the engine's stream; its timing events go to event set `set`.
+    // ---- the stages of a pass, in the order enqueue_pass queues them
+    // reference codes, wide rows, then the annotators: K1 for every read, the wave forms and the cursor form for the reads k_pick_wave lists for them
+    int stage_annotate() {
+        const int64_t n = c.n_reads;
+        if (n <= 0) { if (c.per_lib && c.P > 0) HIPCHK(hipMemsetAsync(d_unavail.p, 0xff, (size_t)c.PS * 4, stream)); return BRC_OK; }
+        Counters* const ctr = d_ctr.p;
+        const int64_t rl = c.ref_hi - c.ref_lo;
+        if (c.has_ref)
+            hipLaunchKernelGGL(k_refcode, dim3((unsigned)(((rl + 2 * REFCODE_PAD + 15) / 16 + 255) / 256)), dim3(256), 0, stream, in.ref, d_refcode.p, rl);
+        if (h_wpairs.n)        // the wide rows of the reads the host found an escape base in
+            hipLaunchKernelGGL(k_wide_rows, dim3((unsigned)((h_wpairs.n + 255) / 256), wide_slices), dim3(256), 0, stream, c, in, d_wpairs.p, (uint32_t)h_wpairs.n, d_bqw.p);
+        DevIn in_k1 = in;
+        if (wave_on || cursor_on) {   // reads with more than two M operators: listed for k_annotate_wave, without operators in K1's copy of the counts (reads with an empty M / = / X operator: for k_annotate_cursor)
+            hipLaunchKernelGGL(k_pick_wave, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c, in, d_nc_k1.p, d_wavelist.p, (uint32_t)n, &ctr->n_wave_reads, &ctr->n_wave_big, &ctr->n_wave_huge,
+                               wave_on ? 1 : 0, cursor_on ? 1 : 0, &ctr->n_literal, &ctr->n_wave_eqx, &ctr->n_wave_eqx_big);
+            in_k1.n_cigar = d_nc_k1.p;
+        }
+        launch_annotate_groups(in_k1);
+        if (wave_on) {
+            // the reads K1 left to the wave form (their number stays on the device: a fixed grid takes them round robin); d_wavelist holds their lists
+            const uint32_t* const wl = d_wavelist.p;
+            const unsigned nb = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)WAVE_FORM_BLOCKS), nb_big = (unsigned)std::min<int64_t>(n, (int64_t)WAVE_FORM_BLOCKS_BIG);
+            launch_annotate_wave<AW_MCAP, 4>(nb, wl, 1, &ctr->n_wave_reads);
+            if (wave_big)       // reads with more than AW_MCAP M operators (more than 2 * AW_MCAP operators): one wave per workgroup, listed from the back
+                launch_annotate_wave<AW_MCAP_BIG, 1>(nb_big, wl + (n - 1), -1, &ctr->n_wave_big);
+            if (wave_eqx) {     // reads with = / X operators: the instantiations that keep the annotator's own cursors; fourth list, the longer ones from its back
+                launch_annotate_wave<AW_MCAP_EQX, 4, true>(nb, wl + (3 * n + 48), 1, &ctr->n_wave_eqx);
+                if (s_max_ncigar > (uint32_t)AW_MCAP_EQX) launch_annotate_wave<AW_MCAP_EQX_BIG, 1, true>(nb_big, wl + (4 * n + 47), -1, &ctr->n_wave_eqx_big);
+            }
+            if (wave_huge)      // more than AW_MCAP_BIG M operators: one wave per CU (its list fills the CU's LDS), second list
+                launch_annotate_wave<AW_MCAP_HUGE, 1>((unsigned)std::min<int64_t>(n, (int64_t)WAVE_FORM_BLOCKS_HUGE), wl + (n + 16), 1, &ctr->n_wave_huge);
+        }
+        if (cursor_on) launch_annotate_cursor();
+        if (c.per_lib) {
+            HIPCHK(hipMemsetAsync(d_unavail.p, 0xff, (size_t)c.PS * 4, stream));
+            hipLaunchKernelGGL(k_unavail, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c, in, d_unavail.p);
+        }
+        return BRC_OK;
+    }
+    // the piece range of every (tile, library): first the running maximum of the piece reaches (block aggregates, their scan) ...
+    bool have_tiles() const { return c.n_pieces > 0 && ntiles > 0; }
+    unsigned reach_blocks() const { return (unsigned)((c.n_pieces + TR_CHUNK - 1) / TR_CHUNK); }
+    void stage_tile_reach() {
+        if (!have_tiles()) return;
+        hipLaunchKernelGGL(k_reach_blockmax, dim3(reach_blocks()), dim3(TR_T), 0, stream, d_keyreach.p, c.n_pieces, d_libbase.p, c.Lp, d_agg.p);
+        hipLaunchKernelGGL((k_scan_aggregates<OpMaxU64>), dim3(1), dim3(1024), 0, stream, d_agg.p, (int64_t)reach_blocks());
+    }
+    // ... then one pass over the pieces of all libraries; the announced windows narrow the ranges of their tiles
+    int stage_tile_ranges() {
+        const int Lp = c.Lp;
+        for (int l = 0; l < Lp && ntiles > 0; ++l)        // (a library without pieces: empty ranges)
+            if (lib_base[(size_t)l + 1] == lib_base[(size_t)l]) HIPCHK(hipMemsetAsync(d_rng.p + (int64_t)l * ntiles, 0, (size_t)ntiles * sizeof(uint2), stream));
+        if (have_tiles())
+            hipLaunchKernelGGL(k_tiles_all, dim3(reach_blocks()), dim3(TR_T), 0, stream, c, d_keyreach.p, c.n_pieces, d_libbase.p, Lp, d_agg.p, ntiles, d_rng.p);
+        const int64_t n_listed = (int64_t)h_tilelist.size();
+        if (has_wanted && n_listed > 0)
+            hipLaunchKernelGGL(k_narrow_tiles, dim3((unsigned)((n_listed * Lp + 255) / 256)), dim3(256), 0, stream, d_wanted.p, d_tilelist.p, n_listed, ntiles, Lp, c.pos0, d_rng.p, d_keyreach.p);
+        kp = {d_pieces.as<const uint4>(), d_rare.p, d_rng.p};
+        return BRC_OK;
+    }
+    // tile compaction: count the live pieces of every (tile, library), scan, (first pass of the region: size the compacted stream — one wait), copy
+    int stage_compact() {
+        if (!compact_on || !have_tiles()) return BRC_OK;
+        int rc; const int64_t np_all = c.n_pieces;
+        const size_t nslot = (size_t)ntiles * (size_t)c.Lp;
+        HIPCHK(d_ccnt.ensure((nslot + 2) * 4)); HIPCHK(d_coff.ensure((nslot + 2) * 4)); HIPCHK(d_crng.ensure((nslot + 1) * sizeof(uint2))); HIPCHK(d_ctot.ensure(24));
+        HIPCHK(hipMemsetAsync(d_ctot.p, 0, 24, stream));
+        HIPCHK(hipMemsetAsync(d_ccnt.p + nslot, 0, 4, stream));
+        // (one library: read-wise, a binary search per read instead of a walk over the whole range; TK_COMPACT=2 keeps the walk)
+        const bool by_read = c.Lp == 1 && !(test_knob(TK_COMPACT) && atoi(test_knob(TK_COMPACT)) == 2);
+        if (by_read) {
+            HIPCHK(hipMemsetAsync(d_ccnt.p, 0, nslot * 4, stream));
+            hipLaunchKernelGGL(k_count_piece_tiles, dim3((unsigned)((np_all + 255) / 256)), dim3(256), 0, stream, c, d_pieces.as<const uint4>(), np_all, d_ccnt.p);
+        } else launch_compact_tiles<true>();
+        if ((rc = scan<OpSumU32, false>(d_ccnt.p, d_coff.p, (int64_t)nslot + 1))) return rc;
+        const bool first_pass = !compact_sized;
+        if (first_pass) {
+            uint32_t tot = 0;
+            HIPCHK(hipMemcpyAsync(&tot, d_coff.p + nslot, 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(h_steps, d_ctot.p, 16, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            compact_total = tot; compact_sized = true;
+            HIPCHK(d_cpieces.ensure(((size_t)compact_total + 4) * sizeof(Piece))); HIPCHK(d_crare.ensure(((size_t)compact_total + 2) * sizeof(PieceRare)));
+        }
+        if (by_read)
+            hipLaunchKernelGGL(k_compact_reads, dim3((unsigned)((ntiles + 4 * CR_GROUP - 1) / (4 * CR_GROUP))), dim3(256), 0, stream, c, d_pieces.as<const uint4>(), d_rare.p, d_rng.p, d_pieceoff.p, d_keyreach.p, ntiles,
+                               d_coff.p, d_cpieces.as<uint4>(), d_crare.p, d_crng.p, d_ctot.p);
+        else launch_compact_tiles<false>();
+        if (by_read && first_pass) {   // (the read-wise copy adds up the piece-steps itself: brc_region_piece_steps reads them after the region's first pass)
+            HIPCHK(hipMemcpyAsync(h_steps, d_ctot.p, 24, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (h_steps[2]) { err = "tile compaction: a tile holds more live read segments than the pass over the segments counted for it"; return BRC_E_HIP; }
+        }
+        kp = {d_cpieces.as<const uint4>(), d_crare.p, d_crng.p};
+#ifdef BRC_CHECKED
+        {   // (the compacted stream exists now: its extents replace K1's for the pileup's sites; the fault count so far is kept)
+            HIPCHK(hipStreamSynchronize(stream));
+            ChkState seen; HIPCHK(hipMemcpy(&seen, d_chk.p, sizeof seen, hipMemcpyDeviceToHost));
+            chk_fill(); ChkState upd = h_chk; upd.count = seen.count; upd.kernel = seen.kernel; upd.site = seen.site; upd.buf = seen.buf; upd.addr = seen.addr; upd.bytes = seen.bytes; upd.unit = seen.unit; upd.piece = seen.piece;
+            HIPCHK(hipMemcpy(d_chk.p, &upd, sizeof upd, hipMemcpyHostToDevice));
+        }
+#endif
+        return BRC_OK;
+    }
+    // third-allele events: one list, then their fold per (position, library, bucket) in column order — the rest of
+    // BasicStat::process_read's accumulation (the host did this until round 6); timed with the counters below
+    int stage_xev_fold() {
+        if (ntiles <= 0) return BRC_OK;
+        int rc; const int64_t nxb = ntiles * c.Lp;
+        HIPCHK(hipMemsetAsync(d_xcnt.p, 0, (size_t)nxb * 4, stream));
+        hipLaunchKernelGGL(k_xev_compact, dim3((unsigned)XEV_SHARDS), dim3(256), 0, stream, d_xev.p, d_xevn.p, (uint32_t)xev_cap, (uint32_t)XEV_SHARDS, d_xevc.p, d_ctr.p, d_xcnt.p, c.Lp);
+        if ((rc = scan<OpSumU32, false>(d_xcnt.p, d_xend.p, nxb))) return rc;
+        hipLaunchKernelGGL(k_xev_scatter, dim3(256), dim3(256), 0, stream, d_xevc.p, d_ctr.p, d_xend.p, d_xidx.p, c.Lp);
+        hipLaunchKernelGGL(k_xev_fold, dim3((unsigned)std::min<int64_t>((nxb + 255) / 256, 2048)), dim3(256), 0, stream, d_xevc.p, d_xcnt.p, d_xend.p, nxb, d_xidx.p, d_xagg.p);
+        return BRC_OK;
+    }
+    void stage_counters() {
+        if (c.P <= 0) return;
+        const unsigned nb = (unsigned)std::min<int64_t>(((c.Lp > 1 ? c.P / 4 : ntiles) + 255) / 256 + 1, c.Lp > 1 ? 4096 : 256);
+        hipLaunchKernelGGL(k_finalize, dim3(nb), dim3(256), 0, stream, c, d_ncol.p, d_tilectr.p, (int64_t)ntiles * c.Lp, d_part.p);
+        hipLaunchKernelGGL(k_finalize_sum, dim3(1), dim3(256), 0, stream, d_part.p, (int)nb, d_ctr.p);
+    }
+    // The indel path (<1 % of the events: keyed count -> scan -> fill -> ordered reduce) depends on K1 only; it follows the pileup
+    // (run under it on a stream of its own, the two only share the machine: the step does not get shorter).  Its three timing slots
+    // are filled from its own events.
+    int stage_indels() {
+        int rc; const int64_t n_buckets = indel_buckets(c);     // indel buckets: (16 or 64 positions, library)
+        HIPCHK(hipEventRecord(ev_indel[0], stream));
+        if ((rc = scan<OpSumU32, false>(d_cnt.p, d_cursor.p, n_buckets))) return rc;
+        HIPCHK(hipEventRecord(ev_indel[1], stream));
+        hipLaunchKernelGGL(k_indel_scatter, dim3((unsigned)((n_indel_cap + 255) / 256)), dim3(256), 0, stream, c, d_evraw.p, (int64_t)n_indel_cap, d_cursor.p, d_ev.p);
+        HIPCHK(hipEventRecord(ev_indel[2], stream));
+        hipLaunchKernelGGL(k_indel_reduce, dim3((unsigned)std::min<int64_t>((n_buckets + 255) / 256, 4096)), dim3(256), 0, stream, c, in, d_reads.p, d_cnt.p, d_cursor.p, n_buckets, d_ev.p, d_unavail.p,
+                           d_iout.p, d_ctr.p);
+        HIPCHK(hipEventRecord(ev_indel[3], stream));
+        return BRC_OK;
+    }
+
+    // One pass of the whole pipeline, queued on the engine's stream; its timing events go to event set `set`: the slot of
+    // kKernelNames[i] lies between evt[i] and evt[i + 1], the three slots of the indel path between its own events.
     int enqueue_pass(size_t set) {
         evt = evsets[set].evt; ev_indel = evsets[set].ev_indel;
-        const int64_t n = c.n_reads, P = c.P; const int Lp = c.Lp;
         int rc;
-        Counters* ctr = (Counters*)d_ctr.p;
-        lists_host = false;
-        HIPCHK(hipMemsetAsync(ctr, 0, sizeof(Counters), stream));
+        lists_host = lists_enqueued = false;
+        HIPCHK(hipMemsetAsync(d_ctr.p, 0, sizeof(Counters), stream));
         HIPCHK(hipMemsetAsync(d_xevn.p, 0, (size_t)XEV_SHARDS * XEV_CTR_STRIDE * 4, stream));
-        const bool indels = n_indel_cap > 0 && P > 0 && n > 0;
-        const int64_t n_buckets = indel_buckets(c);     // indel buckets: (16 or 64 positions, library)
-        if (indels) HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)n_buckets * 4, stream));
+        if (indels_active()) HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)indel_buckets(c) * 4, stream));
 #ifdef BRC_CHECKED
         if (set == 0) { chk_fill(); HIPCHK(hipMemcpyAsync(d_chk.p, &h_chk, sizeof h_chk, hipMemcpyHostToDevice, stream)); HIPCHK(hipStreamSynchronize(stream)); }   // (faults of a ring of passes accumulate in one record)
 #endif
-        Planes pl = {(uint32_t*)d_ncol.p, (uint32_t*)d_depth.p, (uint32_t*)d_slotid.p, (uint32_t*)d_si.p, (float*)d_sf.p, (uint32_t*)d_unavail.p,
-                     (XEv*)d_xev.p, (uint32_t*)d_xevn.p, (uint32_t)xev_cap, (uint32_t)XEV_SHARDS};
-        pl_last = pl;
-        const DRead* reads = (const DRead*)d_reads.p;
+        pl_last = Planes{d_ncol.p, d_depth.p, d_slotid.p, d_si.p, d_sf.p, d_unavail.p, d_xev.p, d_xevn.p, (uint32_t)xev_cap, (uint32_t)XEV_SHARDS};
         HIPCHK(hipEventRecord(evt[T_ANNOTATE], stream));
-        if (n > 0) {
-            const int64_t rl = c.ref_hi - c.ref_lo;
-            if (c.has_ref)
-                hipLaunchKernelGGL(k_refcode, dim3((unsigned)(((rl + 2 * REFCODE_PAD + 15) / 16 + 255) / 256)), dim3(256), 0, stream, in.ref, (uint8_t*)d_refcode.p, rl);
-            if (h_wpairs.n)        // the wide rows of the reads the host found an escape base in
-                hipLaunchKernelGGL(k_wide_rows, dim3((unsigned)((h_wpairs.n + 255) / 256), wide_slices), dim3(256), 0, stream, c, in, (const uint2*)d_wpairs.p, (uint32_t)h_wpairs.n, (uint16_t*)in.bqw);
-            DevIn in_k1 = in;
-            if (wave_on || cursor_on) {   // reads with more than two M operators: listed for k_annotate_wave, without operators in K1's copy of the counts (reads with an empty M / = / X operator: for k_annotate_cursor)
-                hipLaunchKernelGGL(k_pick_wave, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c, in, (uint32_t*)d_nc_k1.p, (uint32_t*)d_wavelist.p, (uint32_t)n, &ctr->n_wave_reads, &ctr->n_wave_big, &ctr->n_wave_huge,
-                                   wave_on ? 1 : 0, cursor_on ? 1 : 0, &ctr->n_literal, &ctr->n_wave_eqx, &ctr->n_wave_eqx_big);
-                in_k1.n_cigar = (const uint32_t*)d_nc_k1.p;
-            }
-            {   // K1: one instantiation per (row layout, width of the narrow packed fields — choose_pack)
-#define BRC_LAUNCH_K1(OS, SH) hipLaunchKernelGGL((k_annotate_groups<OS, SH>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c, in_k1, (DRead*)d_reads.p, (const uint32_t*)d_pieceoff.p, \
-                                   (Piece*)d_pieces.p, (PieceRare*)d_rare.p, (int2*)d_keyreach.p,                                                                               \
-                                   (uint8_t*)in.eb, indels ? (IndelEv*)d_evraw.p : (IndelEv*)nullptr, (uint32_t*)d_cnt.p,                                    \
-                                   in.cigar, in.qual, in.seq4, (const uint8_t*)d_refcode.p + REFCODE_PAD, has_wanted ? (const uint16_t*)d_wanted.p : (const uint16_t*)nullptr)
-                if (Lp == 1) { if (c.pack_shift == 16) BRC_LAUNCH_K1(true, 16); else BRC_LAUNCH_K1(true, 12); }
-                else { if (c.pack_shift == 16) BRC_LAUNCH_K1(false, 16); else BRC_LAUNCH_K1(false, 12); }
-#undef BRC_LAUNCH_K1
-                if (wave_on) {
-                    // the reads K1 left to the wave form (their number stays on the device: a fixed grid takes them round robin)
-                    const unsigned nb = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)WAVE_FORM_BLOCKS);
-#define BRC_LAUNCH_K1W(SH, MCAP, WAVES, GRID, LIST, STEP, COUNT) hipLaunchKernelGGL((k_annotate_wave<SH, MCAP, WAVES>), dim3(GRID), dim3(WAVES * 64), 0, stream, c, in, LIST, STEP, (const unsigned int*)(COUNT),     \
-                                   (DRead*)d_reads.p, (const uint32_t*)d_pieceoff.p, (Piece*)d_pieces.p, (PieceRare*)d_rare.p, (int2*)d_keyreach.p,                                   \
-                                   (uint8_t*)in.eb, indels ? (IndelEv*)d_evraw.p : (IndelEv*)nullptr, (uint32_t*)d_cnt.p,                                          \
-                                   (const uint8_t*)d_refcode.p + REFCODE_PAD, has_wanted ? (const uint16_t*)d_wanted.p : (const uint16_t*)nullptr)
-                    const uint32_t* const wl = (const uint32_t*)d_wavelist.p;
-                    if (c.pack_shift == 16) BRC_LAUNCH_K1W(16, AW_MCAP, 4, nb, wl, 1, &ctr->n_wave_reads); else BRC_LAUNCH_K1W(12, AW_MCAP, 4, nb, wl, 1, &ctr->n_wave_reads);
-                    if (wave_big) {     // reads with more than AW_MCAP M operators (more than 2 * AW_MCAP operators): one wave per workgroup, listed from the back
-                        const unsigned nbb = (unsigned)std::min<int64_t>(n, (int64_t)WAVE_FORM_BLOCKS_BIG);
-                        if (c.pack_shift == 16) BRC_LAUNCH_K1W(16, AW_MCAP_BIG, 1, nbb, wl + (n - 1), -1, &ctr->n_wave_big); else BRC_LAUNCH_K1W(12, AW_MCAP_BIG, 1, nbb, wl + (n - 1), -1, &ctr->n_wave_big);
-                    }
-                    if (wave_eqx) {     // reads with = / X operators: the instantiations that keep the annotator's own cursors; fourth list, the longer ones from its back
-#define BRC_LAUNCH_K1E(SH, MCAP, WAVES, GRID, LIST, STEP, COUNT) hipLaunchKernelGGL((k_annotate_wave<SH, MCAP, WAVES, true>), dim3(GRID), dim3(WAVES * 64), 0, stream, c, in, LIST, STEP, (const unsigned int*)(COUNT),     \
-                                   (DRead*)d_reads.p, (const uint32_t*)d_pieceoff.p, (Piece*)d_pieces.p, (PieceRare*)d_rare.p, (int2*)d_keyreach.p,                                   \
-                                   (uint8_t*)in.eb, indels ? (IndelEv*)d_evraw.p : (IndelEv*)nullptr, (uint32_t*)d_cnt.p,                                          \
-                                   (const uint8_t*)d_refcode.p + REFCODE_PAD, has_wanted ? (const uint16_t*)d_wanted.p : (const uint16_t*)nullptr)
-                        if (c.pack_shift == 16) BRC_LAUNCH_K1E(16, AW_MCAP_EQX, 4, nb, wl + (3 * n + 48), 1, &ctr->n_wave_eqx); else BRC_LAUNCH_K1E(12, AW_MCAP_EQX, 4, nb, wl + (3 * n + 48), 1, &ctr->n_wave_eqx);
-                        if (s_max_ncigar > (uint32_t)AW_MCAP_EQX) {
-                            const unsigned nbe = (unsigned)std::min<int64_t>(n, (int64_t)WAVE_FORM_BLOCKS_BIG);
-                            if (c.pack_shift == 16) BRC_LAUNCH_K1E(16, AW_MCAP_EQX_BIG, 1, nbe, wl + (4 * n + 47), -1, &ctr->n_wave_eqx_big); else BRC_LAUNCH_K1E(12, AW_MCAP_EQX_BIG, 1, nbe, wl + (4 * n + 47), -1, &ctr->n_wave_eqx_big);
-                        }
-#undef BRC_LAUNCH_K1E
-                    }
-                    if (wave_huge) {    // more than AW_MCAP_BIG M operators: one wave per CU (its list fills the CU's LDS), second list
-                        const unsigned nbh = (unsigned)std::min<int64_t>(n, (int64_t)WAVE_FORM_BLOCKS_HUGE);
-                        if (c.pack_shift == 16) BRC_LAUNCH_K1W(16, AW_MCAP_HUGE, 1, nbh, wl + (n + 16), 1, &ctr->n_wave_huge); else BRC_LAUNCH_K1W(12, AW_MCAP_HUGE, 1, nbh, wl + (n + 16), 1, &ctr->n_wave_huge);
-                    }
-#undef BRC_LAUNCH_K1W
-                }
-                if (cursor_on) {
-                    const unsigned nbc = (unsigned)std::min<int64_t>((n + 63) / 64, 1024);
-#define BRC_LAUNCH_K1C(SH) hipLaunchKernelGGL((k_annotate_cursor<SH>), dim3(nbc), dim3(64), 0, stream, c, in, (const uint32_t*)d_wavelist.p + (2 * (size_t)n + 32), (const unsigned int*)&ctr->n_literal,    \
-                                   (DRead*)d_reads.p, (const uint32_t*)d_pieceoff.p, (Piece*)d_pieces.p, (PieceRare*)d_rare.p, (int2*)d_keyreach.p, (uint8_t*)in.eb,                     \
-                                   indels ? (IndelEv*)d_evraw.p : (IndelEv*)nullptr, (uint32_t*)d_cnt.p, has_wanted ? (const uint16_t*)d_wanted.p : (const uint16_t*)nullptr)
-                    if (c.pack_shift == 16) BRC_LAUNCH_K1C(16); else BRC_LAUNCH_K1C(12);
-#undef BRC_LAUNCH_K1C
-                }
-            }
-            if (c.per_lib) {
-                HIPCHK(hipMemsetAsync(d_unavail.p, 0xff, (size_t)c.PS * 4, stream));
-                hipLaunchKernelGGL(k_unavail, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, c, in, (uint32_t*)d_unavail.p);
-            }
-        } else if (c.per_lib && P > 0) HIPCHK(hipMemsetAsync(d_unavail.p, 0xff, (size_t)c.PS * 4, stream));
+        if ((rc = stage_annotate())) return rc;
         HIPCHK(hipEventRecord(evt[T_SCAN_ENDS], stream));
-        // The indel side path (<1 % of the events: keyed count -> scan -> fill -> ordered reduce) depends on K1 only.  It can run
-        // on a stream of its own under the pileup kernel (BRC_INDEL_OVERLAP=1) — measured: the step does not get shorter, the
-        // two only share the machine (k_pileup2 3.75 -> 3.95 ms, step 6.2 ms either way) — so by default it follows the
-        // pileup on the main stream.
-#ifdef BRC_EXP_KNOBS
-        static const bool indel_overlap = getenv("BRC_INDEL_OVERLAP") && atoi(getenv("BRC_INDEL_OVERLAP")) != 0;
-#else
-        const bool indel_overlap = false;
-#endif
-        auto launch_indel = [&](hipStream_t si, DBuf& scratch) -> int {
-            HIPCHK(hipEventRecord(ev_indel[0], si));
-            int r2;
-            if ((r2 = scan_on<OpSumU32, false>((const uint32_t*)d_cnt.p, (uint32_t*)d_cursor.p, n_buckets, si, scratch))) return r2;
-            HIPCHK(hipEventRecord(ev_indel[1], si));
-            hipLaunchKernelGGL(k_indel_scatter, dim3((unsigned)((n_indel_cap + 255) / 256)), dim3(256), 0, si, c, (const IndelEv*)d_evraw.p, (int64_t)n_indel_cap,
-                               (uint32_t*)d_cursor.p, (IndelEv*)d_ev.p);
-            HIPCHK(hipEventRecord(ev_indel[2], si));
-            hipLaunchKernelGGL(k_indel_reduce, dim3((unsigned)std::min<int64_t>((n_buckets + 255) / 256, 4096)), dim3(256), 0, si, c, in, reads,
-                               (const uint32_t*)d_cnt.p, (const uint32_t*)d_cursor.p, n_buckets, (IndelEv*)d_ev.p, (const uint32_t*)d_unavail.p,
-                               (IndelOut*)d_iout.p, ctr);
-            HIPCHK(hipEventRecord(ev_indel[3], si));
-            return BRC_OK;
-        };
-        if (indels && indel_overlap) {
-            HIPCHK(hipStreamWaitEvent(stream3, evt[T_SCAN_ENDS], 0));
-            if ((rc = launch_indel(stream3, d_agg2))) return rc;
-        }
-        // the piece range of every (tile, library): running maximum of the piece reaches (block aggregates, their scan), then
-        // one pass over the pieces of all libraries
-        const int64_t np_all = c.n_pieces;
-        const int64_t trb = (np_all + TR_CHUNK - 1) / TR_CHUNK;
-        if (np_all > 0 && ntiles > 0) {
-            hipLaunchKernelGGL(k_reach_blockmax, dim3((unsigned)trb), dim3(TR_T), 0, stream, (const int2*)d_keyreach.p, np_all, (const int64_t*)d_libbase.p, Lp, (unsigned long long*)d_agg.p);
-            hipLaunchKernelGGL((k_scan_aggregates<OpMaxU64>), dim3(1), dim3(1024), 0, stream, (unsigned long long*)d_agg.p, trb);
-        }
+        stage_tile_reach();
         HIPCHK(hipEventRecord(evt[T_TILES], stream));
-        for (int l = 0; l < Lp && ntiles > 0; ++l)        // (a library without pieces: empty ranges)
-            if (lib_base[(size_t)l + 1] == lib_base[(size_t)l]) HIPCHK(hipMemsetAsync((uint2*)d_rng.p + (int64_t)l * ntiles, 0, (size_t)ntiles * sizeof(uint2), stream));
-        if (np_all > 0 && ntiles > 0)
-            hipLaunchKernelGGL(k_tiles_all, dim3((unsigned)trb), dim3(TR_T), 0, stream, c, (const int2*)d_keyreach.p, np_all, (const int64_t*)d_libbase.p, Lp,
-                               (const unsigned long long*)d_agg.p, ntiles, (uint2*)d_rng.p);
-        const int64_t n_listed = (int64_t)h_tilelist.size();
-        if (has_wanted && n_listed > 0)
-            hipLaunchKernelGGL(k_narrow_tiles, dim3((unsigned)((n_listed * Lp + 255) / 256)), dim3(256), 0, stream, (const uint16_t*)d_wanted.p, (const uint32_t*)d_tilelist.p, n_listed, ntiles, Lp, c.pos0,
-                               (uint2*)d_rng.p, (const int2*)d_keyreach.p);
-        const uint4* kp_pieces = (const uint4*)d_pieces.p; const PieceRare* kp_rare = (const PieceRare*)d_rare.p; const uint2* kp_rng = (const uint2*)d_rng.p;
-        if (compact_on && ntiles > 0 && np_all > 0) {
-            // count the live pieces of every (tile, library), scan, (first pass of the region: size the compacted stream — one wait), copy
-            const size_t nslot = (size_t)ntiles * (size_t)Lp;
-            HIPCHK(d_ccnt.ensure((nslot + 2) * 4)); HIPCHK(d_coff.ensure((nslot + 2) * 4)); HIPCHK(d_crng.ensure((nslot + 1) * sizeof(uint2))); HIPCHK(d_ctot.ensure(24));
-            HIPCHK(hipMemsetAsync(d_ctot.p, 0, 24, stream));
-            HIPCHK(hipMemsetAsync((uint32_t*)d_ccnt.p + nslot, 0, 4, stream));
-            const dim3 cg((unsigned)((ntiles + 3) / 4), (unsigned)Lp);
-            // (one library: read-wise, a binary search per read instead of a walk over the whole range; TK_COMPACT=2 keeps the walk)
-            const bool by_read = Lp == 1 && !(test_knob(TK_COMPACT) && atoi(test_knob(TK_COMPACT)) == 2);
-            if (by_read) {
-                HIPCHK(hipMemsetAsync(d_ccnt.p, 0, nslot * 4, stream));
-                hipLaunchKernelGGL(k_count_piece_tiles, dim3((unsigned)((np_all + 255) / 256)), dim3(256), 0, stream, c, (const uint4*)d_pieces.p, np_all, (uint32_t*)d_ccnt.p);
-            }
-            else
-            hipLaunchKernelGGL((k_compact_tiles<true>), cg, dim3(256), 0, stream, c, (const uint4*)d_pieces.p, (const PieceRare*)d_rare.p, (const uint2*)d_rng.p, ntiles,
-                               (uint32_t*)d_ccnt.p, (const uint32_t*)nullptr, (uint4*)nullptr, (PieceRare*)nullptr, (uint2*)nullptr, (unsigned long long*)d_ctot.p);
-            if ((rc = scan<OpSumU32, false>((const uint32_t*)d_ccnt.p, (uint32_t*)d_coff.p, (int64_t)nslot + 1))) return rc;
-            const bool first_pass = !compact_sized;
-            if (!compact_sized) {
-                uint32_t tot = 0;
-                HIPCHK(hipMemcpyAsync(&tot, (const uint32_t*)d_coff.p + nslot, 4, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipMemcpyAsync(h_steps, d_ctot.p, 16, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                compact_total = tot; compact_sized = true;
-                HIPCHK(d_cpieces.ensure(((size_t)compact_total + 4) * sizeof(Piece))); HIPCHK(d_crare.ensure(((size_t)compact_total + 2) * sizeof(PieceRare)));
-            }
-            if (by_read)
-                hipLaunchKernelGGL(k_compact_reads, dim3((unsigned)((ntiles + 4 * CR_GROUP - 1) / (4 * CR_GROUP))), dim3(256), 0, stream, c, (const uint4*)d_pieces.p, (const PieceRare*)d_rare.p, (const uint2*)d_rng.p, (const uint32_t*)d_pieceoff.p, (const int2*)d_keyreach.p, ntiles,
-                                   (const uint32_t*)d_coff.p, (uint4*)d_cpieces.p, (PieceRare*)d_crare.p, (uint2*)d_crng.p, (unsigned long long*)d_ctot.p);
-            else
-            hipLaunchKernelGGL((k_compact_tiles<false>), cg, dim3(256), 0, stream, c, (const uint4*)d_pieces.p, (const PieceRare*)d_rare.p, (const uint2*)d_rng.p, ntiles,
-                               (uint32_t*)d_ccnt.p, (const uint32_t*)d_coff.p, (uint4*)d_cpieces.p, (PieceRare*)d_crare.p, (uint2*)d_crng.p, (unsigned long long*)d_ctot.p);
-            if (by_read && first_pass) {   // (the read-wise copy adds up the piece-steps itself: brc_region_piece_steps reads them after the region's first pass)
-                HIPCHK(hipMemcpyAsync(h_steps, d_ctot.p, 24, hipMemcpyDeviceToHost, stream));
-                HIPCHK(hipStreamSynchronize(stream));
-                if (h_steps[2]) { err = "tile compaction: a tile holds more live read segments than the pass over the segments counted for it"; return BRC_E_HIP; }
-            }
-            kp_pieces = (const uint4*)d_cpieces.p; kp_rare = (const PieceRare*)d_crare.p; kp_rng = (const uint2*)d_crng.p;
-#ifdef BRC_CHECKED
-            {   // (the compacted stream exists now: its extents replace K1's for the pileup's sites; the fault count so far is kept)
-                HIPCHK(hipStreamSynchronize(stream));
-                ChkState seen; HIPCHK(hipMemcpy(&seen, d_chk.p, sizeof seen, hipMemcpyDeviceToHost));
-                chk_fill(); ChkState upd = h_chk; upd.count = seen.count; upd.kernel = seen.kernel; upd.site = seen.site; upd.buf = seen.buf; upd.addr = seen.addr; upd.bytes = seen.bytes; upd.unit = seen.unit; upd.piece = seen.piece;
-                HIPCHK(hipMemcpy(d_chk.p, &upd, sizeof upd, hipMemcpyHostToDevice));
-            }
-#endif
-        }
+        if ((rc = stage_tile_ranges()) || (rc = stage_compact())) return rc;
         HIPCHK(hipEventRecord(evt[T_PILEUP], stream));
-        if (ntiles > 0) {
-            unsigned nwg = (unsigned)(((has_wanted ? n_listed : ntiles) + PILEUP_WAVES - 1) / PILEUP_WAVES);
-            nwg = (nwg + 7u) & ~7u;
-            // profiling knob: unused dynamic LDS lowers the number of resident waves (occupancy sweeps)
-#ifdef BRC_EXP_KNOBS
-            static const unsigned dyn_lds = getenv("BRC_PILEUP_LDS_PAD") ? (unsigned)atoi(getenv("BRC_PILEUP_LDS_PAD")) : 0u;
-#else
-            const unsigned dyn_lds = 0u;
-#endif
-#define BRC_LAUNCH_KP(W, SH) hipLaunchKernelGGL((k_pileup2<W, SH>), dim3(nwg, (unsigned)Lp), dim3(PILEUP_WAVES * 64), dyn_lds, stream, c, in, kp_pieces, kp_rare, \
-                               kp_rng, ntiles, pl, (uint4*)d_tilectr.p, in.eb, in.bqw, (const uint32_t*)d_unavail.p,                                                     \
-                               (const uint8_t*)d_refcode.p + REFCODE_PAD, (const uint16_t*)d_wanted.p, (const uint32_t*)d_tilelist.p, n_listed)
-            if (has_wanted) { if (n_listed > 0) { if (c.pack_shift == 16) BRC_LAUNCH_KP(true, 16); else BRC_LAUNCH_KP(true, 12); } }
-            else { if (c.pack_shift == 16) BRC_LAUNCH_KP(false, 16); else BRC_LAUNCH_KP(false, 12); }
-#undef BRC_LAUNCH_KP
-        }
+        stage_pileup();
         HIPCHK(hipEventRecord(evt[T_COUNT], stream));      // (the k_pileup slot is k_pileup2 alone: what rocprofv3's average for the kernel must agree with)
-        if (ntiles > 0) {
-            // third-allele events: one list, then their fold per (position, library, bucket) in column order — the rest of
-            // BasicStat::process_read's accumulation (the host did this until round 6); timed with the counters below
-            const int64_t nxb = ntiles * Lp;
-            HIPCHK(hipMemsetAsync(d_xcnt.p, 0, (size_t)nxb * 4, stream));
-            hipLaunchKernelGGL(k_xev_compact, dim3((unsigned)XEV_SHARDS), dim3(256), 0, stream, (const XEv*)d_xev.p, (const uint32_t*)d_xevn.p, (uint32_t)xev_cap,
-                               (uint32_t)XEV_SHARDS, (XEv*)d_xevc.p, ctr, (uint32_t*)d_xcnt.p, Lp);
-            if ((rc = scan<OpSumU32, false>((const uint32_t*)d_xcnt.p, (uint32_t*)d_xend.p, nxb))) return rc;
-            hipLaunchKernelGGL(k_xev_scatter, dim3(256), dim3(256), 0, stream, (const XEv*)d_xevc.p, (const Counters*)ctr, (uint32_t*)d_xend.p, (uint32_t*)d_xidx.p, Lp);
-            hipLaunchKernelGGL(k_xev_fold, dim3((unsigned)std::min<int64_t>((nxb + 255) / 256, 2048)), dim3(256), 0, stream, (const XEv*)d_xevc.p, (uint32_t*)d_xcnt.p, (uint32_t*)d_xend.p, nxb,
-                               (uint32_t*)d_xidx.p, (XAgg*)d_xagg.p);
-        }
-        if (P > 0) {
-            const unsigned nb = (unsigned)std::min<int64_t>(((Lp > 1 ? P / 4 : ntiles) + 255) / 256 + 1, Lp > 1 ? 4096 : 256);
-            hipLaunchKernelGGL(k_finalize, dim3(nb), dim3(256), 0, stream, c, (const uint32_t*)d_ncol.p, (const uint4*)d_tilectr.p, (int64_t)ntiles * Lp,
-                               (unsigned long long*)d_part.p);
-            hipLaunchKernelGGL(k_finalize_sum, dim3(1), dim3(256), 0, stream, (const unsigned long long*)d_part.p, (int)nb, ctr);
-        }
+        if ((rc = stage_xev_fold())) return rc;
+        stage_counters();
         HIPCHK(hipEventRecord(evt[T_INDEL_SCAN], stream));
-        // (the timing slots of the indel path's three stages are filled from its own events)
-        if (indels && !indel_overlap) { if ((rc = launch_indel(stream, d_agg))) return rc; }
-        if (indels && indel_overlap) HIPCHK(hipStreamWaitEvent(stream, ev_indel[3], 0));
+        if (indels_active() && (rc = stage_indels())) return rc;
         HIPCHK(hipEventRecord(evt[T_N], stream));
         HIPCHK(hipGetLastError());
         return BRC_OK;
@@ -2779,18 +2796,16 @@ class HipBackend : public Backend {
 #endif
         if ((size_t)h_ctr.xev_max > xev_cap) {
             xev_cap = (size_t)h_ctr.xev_max * 2;
-            HIPCHK(d_xev.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * sizeof(XEv))); HIPCHK(d_xevc.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * sizeof(XEv)));
-            HIPCHK(d_xidx.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * 4)); HIPCHK(d_xagg.ensure(((size_t)XEV_SHARDS * xev_cap + 1) * sizeof(XAgg)));
+            const int rc = ensure_xev_lists(); if (rc) return rc;
             *again = true;
         }
         return BRC_OK;
     }
     // adds the per-kernel times of the pass recorded in event set `set` to t (slots and total)
     int add_timing(size_t set, brc_timing* t) {
-        const bool indels = n_indel_cap > 0 && c.P > 0 && c.n_reads > 0;
         const EvSet& es = evsets[set]; float ms = 0;
         for (int i = 0; i < T_INDEL_SCAN; ++i) { HIPCHK(hipEventElapsedTime(&ms, es.evt[i], es.evt[i + 1])); t->ms[i] += ms; }
-        if (indels) for (int i = 0; i < 3; ++i) { HIPCHK(hipEventElapsedTime(&ms, es.ev_indel[i], es.ev_indel[i + 1])); t->ms[T_INDEL_SCAN + i] += ms; }
+        if (indels_active()) for (int i = 0; i < 3; ++i) { HIPCHK(hipEventElapsedTime(&ms, es.ev_indel[i], es.ev_indel[i + 1])); t->ms[T_INDEL_SCAN + i] += ms; }
         HIPCHK(hipEventElapsedTime(&ms, es.evt[0], es.evt[T_N])); t->total_ms += ms;
         return BRC_OK;
     }
@@ -2849,20 +2864,19 @@ class HipBackend : public Backend {
         // the download before this one read d_toff / d_text on the copy stream: it is long done, but say so to the device
         HIPCHK(hipStreamWaitEvent(stream, ev_text[slot ^ 1], 0));
         HIPCHK(hipMemcpyAsync(d_tctx.p, ctx.data(), ctx.size(), hipMemcpyHostToDevice, stream));
-        TextCtx t; t.lib_off = (const int32_t*)d_tctx.p; t.chrom = (const char*)d_tctx.p + ob; t.chrom_len = (int32_t)chrom.size(); t.lib_names = t.chrom;
+        TextCtx t; t.lib_off = d_tctx.as<const int32_t>(); t.chrom = d_tctx.p + ob; t.chrom_len = (int32_t)chrom.size(); t.lib_names = t.chrom;
         const unsigned nb = (unsigned)((P + 1 + 255) / 256);
-        const bool indels = n_indel_cap > 0 && c.P > 0 && c.n_reads > 0;
         TextAux ax; memset(&ax, 0, sizeof ax);
-        ax.xagg = (const XAgg*)d_xagg.p; ax.xagg_end = (const uint32_t*)d_xend.p; ax.xagg_cnt = (const uint32_t*)d_xcnt.p;
-        if (indels) { ax.iout = (const IndelOut*)d_iout.p; ax.ib_end = (const uint32_t*)d_cursor.p; ax.ib_cnt = (const uint32_t*)d_cnt.p; ax.reads = (const DRead*)d_reads.p; }
-        hipLaunchKernelGGL(k_text_len, dim3(nb), dim3(256), 0, stream, c, in, pl_last, t, ax, (uint32_t*)d_tlen.p);
+        ax.xagg = d_xagg.p; ax.xagg_end = d_xend.p; ax.xagg_cnt = d_xcnt.p;
+        if (indels_active()) { ax.iout = d_iout.p; ax.ib_end = d_cursor.p; ax.ib_cnt = d_cnt.p; ax.reads = d_reads.p; }
+        hipLaunchKernelGGL(k_text_len, dim3(nb), dim3(256), 0, stream, c, in, pl_last, t, ax, d_tlen.p);
         int rc;
-        if ((rc = scan<OpSumU32, false>((const uint32_t*)d_tlen.p, (uint32_t*)d_toff.p, P + 1))) return rc;
+        if ((rc = scan<OpSumU32, false>(d_tlen.p, d_toff.p, P + 1))) return rc;
         // the 32-bit total, and the true one: the caller's estimate of the text size (brc_host.cpp) does not know the lengths of the
         // library names or of sums at the far end of int32 — a region whose lines pass 4 GiB is handed back for the host formatter
         HIPCHK(d_total64.ensure(16)); HIPCHK(hipMemsetAsync(d_total64.p, 0, 8, stream));
-        hipLaunchKernelGGL(k_text_total, dim3((unsigned)std::min<int64_t>((P + 255) / 256, 1024)), dim3(256), 0, stream, (const uint32_t*)d_tlen.p, P, (unsigned long long*)d_total64.p);
-        HIPCHK(hipMemcpyAsync(h_total.p, (const uint32_t*)d_toff.p + P, 4, hipMemcpyDeviceToHost, stream));
+        hipLaunchKernelGGL(k_text_total, dim3((unsigned)std::min<int64_t>((P + 255) / 256, 1024)), dim3(256), 0, stream, d_tlen.p, P, d_total64.p);
+        HIPCHK(hipMemcpyAsync(h_total.p, d_toff.p + P, 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(h_total.p + 2, d_total64.p, 8, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));                                  // (also covers the local `ctx`)
         const uint64_t total = h_total.p[0];
@@ -2874,10 +2888,10 @@ class HipBackend : public Backend {
         std::lock_guard<std::mutex> lk(text_mu);
         HIPCHK(d_text.ensure((size_t)total + 64));
         if (!h_text[slot].reserve((size_t)total + 64)) { err = "pinned host allocation failed"; return BRC_E_NOMEM; }
-        hipLaunchKernelGGL(k_text_write, dim3(nb), dim3(256), 0, stream, c, in, pl_last, t, ax, (const uint32_t*)d_toff.p, (char*)d_text.p);
+        hipLaunchKernelGGL(k_text_write, dim3(nb), dim3(256), 0, stream, c, in, pl_last, t, ax, d_toff.p, d_text.p);
         // the last position every library was processed at: the host's account of what the region leaves in the deletion queues
         HIPCHK(d_lastproc.ensure((size_t)c.Lp * 4 + 16));
-        hipLaunchKernelGGL(k_last_processed, dim3((unsigned)c.Lp), dim3(256), 0, stream, c, (const uint32_t*)d_ncol.p, (const uint32_t*)d_unavail.p, (uint32_t*)d_lastproc.p);
+        hipLaunchKernelGGL(k_last_processed, dim3((unsigned)c.Lp), dim3(256), 0, stream, c, d_ncol.p, d_unavail.p, d_lastproc.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev_lines, stream));
         // the copies run on their own stream: uploads and kernels of the next region do not queue behind 300 MB of text
@@ -2911,8 +2925,7 @@ class HipBackend : public Backend {
     int device_view(brc_device_view* out) override {
         if (!computed) { err = "not computed"; return BRC_E_ARG; }
         out->memory = BRC_MEM_DEVICE; out->device = device;
-        out->ncol = (const uint32_t*)d_ncol.p; out->depth = (const uint32_t*)d_depth.p; out->slotid = (const uint32_t*)d_slotid.p;
-        out->si = (const uint32_t*)d_si.p; out->sf = (const float*)d_sf.p; out->unavail = (const uint32_t*)d_unavail.p;
+        out->ncol = d_ncol.p; out->depth = d_depth.p; out->slotid = d_slotid.p; out->si = d_si.p; out->sf = d_sf.p; out->unavail = d_unavail.p;
         out->xagg = d_xagg.p; out->n_xagg = h_ctr.n_xev;
         return BRC_OK;
     }
@@ -2920,56 +2933,32 @@ class HipBackend : public Backend {
     // and the device copies of what spells their alleles — the reads' SEQ as uploaded, the reference slice
     int device_indels(const Staged&, const Geometry&, brc_device_indels* out) override {
         if (!computed) { err = "not computed"; return BRC_E_ARG; }
-        const bool indels = n_indel_cap > 0 && c.P > 0 && c.n_reads > 0;
         out->memory = BRC_MEM_DEVICE; out->device = device;
-        out->n_slots = indels ? h_ctr.n_indel_slots : 0u; out->slots = out->n_slots ? d_iout.p : nullptr;
-        out->seq4 = (const uint8_t*)d_seq.p; out->seq_off = (const uint64_t*)d_so.p; out->l_qseq = (const int32_t*)d_lq.p; out->n_reads = c.n_reads;
-        out->ref = c.has_ref ? (const char*)d_ref.p : nullptr;
+        out->n_slots = indels_active() ? h_ctr.n_indel_slots : 0u; out->slots = out->n_slots ? d_iout.p : nullptr;
+        out->seq4 = d_seq.p; out->seq_off = d_so.p; out->l_qseq = d_lq.p; out->n_reads = c.n_reads;
+        out->ref = c.has_ref ? d_ref.p : nullptr;
         return BRC_OK;
     }
 
-    // brc_fetch_window: the compact planes of plane indices [k0, k0 + n) -> pinned window buffers (strided copies: a plane
-    // row of n elements out of every PS), the region's two lists whole (downloaded once per computed region)
-    HBuf<uint32_t> w_ncol, w_depth, w_slotid, w_si, w_unavail; HBuf<float> w_sf; bool w_init = false;
-    bool lists_host = false;             // h_xev / h_iout / iout_compact hold the lists of the last compute
-    int fetch_window(int64_t k0, int64_t n, HostPlanes* out, int64_t* stride) override {
-        HIPCHK(hipSetDevice(device));
-        if (!computed) { err = "not computed"; return BRC_E_ARG; }
-        if (k0 < 0 || n < 0 || k0 + n > c.P) { err = "window outside the planes"; return BRC_E_ARG; }
-        if (!w_init) { w_ncol.A = w_depth.A = w_slotid.A = w_si.A = w_unavail.A = &kPinned; w_sf.A = &kPinned; w_init = true; }
-        const size_t WS = (size_t)((n + 63) & ~(int64_t)63), Lp = (size_t)c.Lp, PS = (size_t)c.PS;
-        if (!w_ncol.reserve(Lp * WS + 4) || !w_depth.reserve(Lp * WS + 4) || !w_slotid.reserve(Lp * WS + 4) || !w_unavail.reserve(WS + 4) ||
-            !w_si.reserve(Lp * 2 * NI * WS + 4) || !w_sf.reserve(Lp * 2 * NF * WS + 4)) { err = "pinned host allocation failed"; return BRC_E_NOMEM; }
+    // The six result planes -> the page-locked buffers of h, queued on the engine's stream: of every plane row (PS elements on the
+    // device) the n elements from k0 on, rows WS elements apart on the host.  brc_fetch takes whole rows (one contiguous copy per
+    // plane), brc_fetch_window a strided copy.
+    int copy_planes(HostSet& h, int64_t k0, size_t n, size_t WS, bool strided, HostPlanes* out) {
+        const size_t Lp = (size_t)c.Lp, PS = (size_t)c.PS;
+        if (!h.ncol.reserve(Lp * WS + 4) || !h.depth.reserve(Lp * WS + 4) || !h.slotid.reserve(Lp * WS + 4) || !h.unavail.reserve(WS + 4) ||
+            !h.si.reserve(Lp * 2 * NI * WS + 4) || !h.sf.reserve(Lp * 2 * NF * WS + 4)) { err = "pinned host allocation failed"; return BRC_E_NOMEM; }
+        const struct { void* host; const uint32_t* dev; size_t rows; } planes[] = {
+            {h.ncol.p, d_ncol.p, Lp}, {h.depth.p, d_depth.p, Lp}, {h.slotid.p, d_slotid.p, Lp}, {h.si.p, d_si.p, Lp * 2 * NI}, {h.sf.p, d_sf.as<const uint32_t>(), Lp * 2 * NF}};
         if (n) {
-            const size_t wb = (size_t)n * 4;
-            HIPCHK(hipMemcpy2DAsync(w_ncol.p, WS * 4, (const uint32_t*)d_ncol.p + k0, PS * 4, wb, Lp, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpy2DAsync(w_depth.p, WS * 4, (const uint32_t*)d_depth.p + k0, PS * 4, wb, Lp, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpy2DAsync(w_slotid.p, WS * 4, (const uint32_t*)d_slotid.p + k0, PS * 4, wb, Lp, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpy2DAsync(w_si.p, WS * 4, (const uint32_t*)d_si.p + k0, PS * 4, wb, Lp * 2 * NI, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpy2DAsync(w_sf.p, WS * 4, (const float*)d_sf.p + k0, PS * 4, wb, Lp * 2 * NF, hipMemcpyDeviceToHost, stream));
-            if (c.per_lib) HIPCHK(hipMemcpyAsync(w_unavail.p, (const uint32_t*)d_unavail.p + k0, wb, hipMemcpyDeviceToHost, stream));
+            for (const auto& q : planes)
+                HIPCHK(strided ? hipMemcpy2DAsync(q.host, WS * 4, q.dev + k0, PS * 4, n * 4, q.rows, hipMemcpyDeviceToHost, stream) : hipMemcpyAsync(q.host, q.dev, q.rows * n * 4, hipMemcpyDeviceToHost, stream));
+            if (c.per_lib) HIPCHK(hipMemcpyAsync(h.unavail.p, d_unavail.p + k0, n * 4, hipMemcpyDeviceToHost, stream));
         }
-        if (!lists_host) {
-            const int rc = enqueue_lists(); if (rc) return rc;
-            lists_enqueued = false;
-            HIPCHK(hipStreamSynchronize(stream));
-            iout_compact.clear();
-            for (size_t i = 0; i < (size_t)h_ctr.n_indel_slots; ++i) if (h_iout.p[i].len != 0) iout_compact.push_back(h_iout.p[i]);
-            xagg_compact.clear();
-            for (size_t i = 0; i < (size_t)h_ctr.n_xev; ++i) if (h_xagg.p[i].k != NONE32) xagg_compact.push_back(h_xagg.p[i]);
-            lists_host = true;
-        } else HIPCHK(hipStreamSynchronize(stream));
-        *out = HostPlanes();
-        out->ncol = w_ncol.p; out->depth = w_depth.p; out->slotid = w_slotid.p; out->si = w_si.p; out->sf = w_sf.p; out->unavail = w_unavail.p;
-        out->xagg = xagg_compact.data(); out->n_xagg = xagg_compact.size();
-        out->indel = iout_compact.data(); out->n_indel = (int64_t)iout_compact.size();
-        out->n_events = h_ctr.n_events; out->n_positions = h_ctr.n_positions;
-        *stride = (int64_t)WS;
+        out->ncol = h.ncol.p; out->depth = h.depth.p; out->slotid = h.slotid.p; out->si = h.si.p; out->sf = h.sf.p; out->unavail = h.unavail.p;
         return BRC_OK;
     }
     // the two small lists (third-allele events, indel buckets) -> pinned host memory.  With device-side text they are
     // requested BEFORE the text: the DMA engine serves copies in order, and the caller needs the lists first.
-    bool lists_enqueued = false;
     int enqueue_lists() {
         const size_t nx = h_ctr.n_xev, ns = h_ctr.n_indel_slots;
         if (!h_xagg.reserve(nx + 4) || !h_iout.reserve(ns + 4)) { err = "pinned host allocation failed"; return BRC_E_NOMEM; }
@@ -2978,9 +2967,29 @@ class HipBackend : public Backend {
         lists_enqueued = true;
         return BRC_OK;
     }
-    // pinned / device room for the text of regions of about `bytes` (called early, from any thread, before the first region)
+    // waits for the engine's stream (the copies queued on it) with the two lists of the last compute on the host, their used entries
+    // compacted (once per computed region, unless they were requested anew), and fills the list, counter and warning fields of out
+    int lists_to_host(HostPlanes* out) {
+        const bool fresh = !lists_host || lists_enqueued;
+        if (fresh && !lists_enqueued) { const int rc = enqueue_lists(); if (rc) return rc; }
+        lists_enqueued = false;
+        HIPCHK(hipStreamSynchronize(stream));
+        if (fresh) {
+            iout_compact.clear();
+            for (size_t i = 0; i < (size_t)h_ctr.n_indel_slots; ++i) if (h_iout.p[i].len != 0) iout_compact.push_back(h_iout.p[i]);
+            xagg_compact.clear();
+            for (size_t i = 0; i < (size_t)h_ctr.n_xev; ++i) if (h_xagg.p[i].k != NONE32) xagg_compact.push_back(h_xagg.p[i]);
+            lists_host = true;
+        }
+        out->xagg = xagg_compact.data(); out->n_xagg = xagg_compact.size();
+        out->indel = iout_compact.data(); out->n_indel = (int64_t)iout_compact.size();
+        out->n_events = h_ctr.n_events; out->n_positions = h_ctr.n_positions;
+        out->warn[BRC_W_SM_MISSING] = h_ctr.w_sm; out->warn[BRC_W_NM_MISSING] = h_ctr.w_nm; out->warn[BRC_W_ZM_MISSING] = 0;
+        out->warn[BRC_W_LIB_UNAVAILABLE] = h_ctr.w_lib;
+        return BRC_OK;
+    }
     void list_sizes(uint64_t* n_xev, uint64_t* n_indel_slots) override { *n_xev = h_ctr.n_xev; *n_indel_slots = h_ctr.n_indel_slots; }
-    std::mutex text_mu;                  // reserve_text may run on another thread while the first region is staged
+    // pinned / device room for the text of regions of about `bytes` (called early, from any thread, before the first region)
     int reserve_text(size_t bytes) override {
         std::lock_guard<std::mutex> lk(text_mu);
         HIPCHK(hipSetDevice(device));
@@ -2988,37 +2997,25 @@ class HipBackend : public Backend {
         HIPCHK(d_text.ensure(bytes));
         return BRC_OK;
     }
+    // brc_fetch: the planes whole, with their padded stride (planes == false: the lists and counters alone)
     int fetch(HostPlanes* out, bool planes) override {
         HIPCHK(hipSetDevice(device));
         if (!computed) { err = "not computed"; return BRC_E_ARG; }
-        const size_t P = planes ? (size_t)c.PS : 0, Lp = (size_t)c.Lp;   // planes are copied with their padded stride
-        const size_t nx = h_ctr.n_xev;
-        if (!h_ncol.reserve(Lp * P + 4) || !h_depth.reserve(Lp * P + 4) || !h_slotid.reserve(Lp * P + 4) || !h_unavail.reserve(P + 4) ||
-            !h_si.reserve(Lp * 2 * NI * P + 4) || !h_sf.reserve(Lp * 2 * NF * P + 4)) { err = "pinned host allocation failed"; return BRC_E_NOMEM; }
-        if (P) {
-            HIPCHK(hipMemcpyAsync(h_ncol.p, d_ncol.p, Lp * P * 4, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(h_depth.p, d_depth.p, Lp * P * 4, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(h_slotid.p, d_slotid.p, Lp * P * 4, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(h_si.p, d_si.p, Lp * 2 * NI * P * 4, hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipMemcpyAsync(h_sf.p, d_sf.p, Lp * 2 * NF * P * 4, hipMemcpyDeviceToHost, stream));
-            if (c.per_lib) HIPCHK(hipMemcpyAsync(h_unavail.p, d_unavail.p, P * 4, hipMemcpyDeviceToHost, stream));
-        }
-        const size_t ns = h_ctr.n_indel_slots;
-        if (!lists_enqueued) { const int rc = enqueue_lists(); if (rc) return rc; }
-        lists_enqueued = false;
-        HIPCHK(hipStreamSynchronize(stream));
-        iout_compact.clear();
-        for (size_t i = 0; i < ns; ++i) if (h_iout.p[i].len != 0) iout_compact.push_back(h_iout.p[i]);
-        xagg_compact.clear();
-        for (size_t i = 0; i < nx; ++i) if (h_xagg.p[i].k != NONE32) xagg_compact.push_back(h_xagg.p[i]);
-        lists_host = true;
-        out->ncol = h_ncol.p; out->depth = h_depth.p; out->slotid = h_slotid.p; out->si = h_si.p; out->sf = h_sf.p; out->unavail = h_unavail.p;
-        out->xagg = xagg_compact.data(); out->n_xagg = xagg_compact.size();
-        out->indel = iout_compact.data(); out->n_indel = (int64_t)iout_compact.size();
-        out->n_events = h_ctr.n_events; out->n_positions = h_ctr.n_positions;
-        out->warn[BRC_W_SM_MISSING] = h_ctr.w_sm; out->warn[BRC_W_NM_MISSING] = h_ctr.w_nm; out->warn[BRC_W_ZM_MISSING] = 0;
-        out->warn[BRC_W_LIB_UNAVAILABLE] = h_ctr.w_lib;
-        return BRC_OK;
+        const size_t P = planes ? (size_t)c.PS : 0;
+        const int rc = copy_planes(h_pl, 0, P, P, false, out); if (rc) return rc;
+        return lists_to_host(out);
+    }
+    // brc_fetch_window: the compact planes of plane indices [k0, k0 + n) -> pinned window buffers (a plane row of n elements
+    // out of every PS), the region's two lists whole (downloaded once per computed region)
+    int fetch_window(int64_t k0, int64_t n, HostPlanes* out, int64_t* stride) override {
+        HIPCHK(hipSetDevice(device));
+        if (!computed) { err = "not computed"; return BRC_E_ARG; }
+        if (k0 < 0 || n < 0 || k0 + n > c.P) { err = "window outside the planes"; return BRC_E_ARG; }
+        const size_t WS = (size_t)((n + 63) & ~(int64_t)63);
+        *out = HostPlanes();
+        const int rc = copy_planes(w_pl, k0, (size_t)n, WS, true, out); if (rc) return rc;
+        *stride = (int64_t)WS;
+        return lists_to_host(out);
     }
 };
 
