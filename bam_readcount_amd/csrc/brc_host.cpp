@@ -22,9 +22,9 @@
 #include <deque>
 #include <thread>
 #include <functional>
+#include <memory>
 #include <queue>
 #include <condition_variable>
-#include <functional>
 
 namespace brc {
 
@@ -98,17 +98,19 @@ class Pool {
     }
 };
 
-void Staged::init(const HostAlloc* A) {
-    pos.A = A; flag.A = A; mapq.A = A; lib.A = A; l_qseq.A = A; n_cigar.A = A; cig_off.A = A; seq_off.A = A; qual_off.A = A;
-    nm.A = A; sm.A = A; tags.A = A; cigar.A = A; seq4.A = A; qual.A = A; bq_row.A = A; wide.A = A; piece_cnt.A = A; piece_off.A = A; iev_off.A = A; qnames.A = A; qname_off.A = A;
-}
+void Staged::init(const HostAlloc* A) { each_buf([A](auto& h) { h.A = A; }); }
 void Staged::clear() {
-    pos.clear(); flag.clear(); mapq.clear(); lib.clear(); l_qseq.clear(); n_cigar.clear(); cig_off.clear(); seq_off.clear();
-    qual_off.clear(); nm.clear(); sm.clear(); tags.clear(); cigar.clear(); seq4.clear(); qual.clear(); bq_row.clear(); wide.clear();
+    each_buf([](auto& h) { h.clear(); });
     bq_elems = 0; memset(len_hist, 0, sizeof len_hist); n = 0; min_pos = 0; max_end = 0; n_indel_ops = 0;
     seq_seg.clear(); qual_seg.clear(); seq_total = 0; qual_total = 0;
-    piece_cnt.clear(); piece_off.clear(); iev_off.clear(); lib_base.clear(); n_pieces = 0; max_lqseq = 0; max_ncigar = 0; has_empty_m = false; has_eqx = false; max_span = 0; qnames.clear(); qname_off.clear();
+    lib_base.clear(); n_pieces = 0; max_lqseq = 0; max_ncigar = 0; has_empty_m = false; has_eqx = false; max_span = 0;
     win_beg.clear(); win_end.clear();
+}
+void Staged::destroy() { each_buf([](auto& h) { h.destroy(); }); }
+bool Staged::reserve_reads(size_t reads, size_t cigar_ops) {
+    bool ok = cigar.reserve(cigar_ops);
+    each_read_buf([&](auto& h) { ok = ok && h.reserve(reads); });
+    return ok;
 }
 std::vector<uint16_t> Staged::wanted_tiles(int32_t pos0, int64_t P) const {
     std::vector<uint16_t> w;
@@ -127,11 +129,6 @@ std::vector<uint16_t> Staged::wanted_tiles(int32_t pos0, int64_t P) const {
         }
     }
     return w;
-}
-void Staged::destroy() {
-    pos.destroy(); flag.destroy(); mapq.destroy(); lib.destroy(); l_qseq.destroy(); n_cigar.destroy(); cig_off.destroy();
-    seq_off.destroy(); qual_off.destroy(); nm.destroy(); sm.destroy(); tags.destroy(); cigar.destroy(); seq4.destroy(); qual.destroy(); bq_row.destroy(); wide.destroy();
-    piece_cnt.destroy(); piece_off.destroy(); iev_off.destroy(); qnames.destroy(); qname_off.destroy();
 }
 // library-major slots: all pieces of library 0 in file order, then library 1, ... (one stream without -p)
 void Staged::layout_pieces(int Lp, bool per_lib) {
@@ -362,6 +359,24 @@ struct TextBuf {
     }
 };
 
+// A dense result: the ABI's planes (grow-only, every element written by expand_slots) and the lists handed out with them.  The
+// engine has two — the region's and brc_fetch_window's, so that a window leaves a fetched whole-region result as it was.
+struct DenseResult {
+    uint32_t* i = nullptr; float* f = nullptr; size_t cap = 0;        // istat / fstat, `cap` elements per statistic
+    std::vector<brc_indel> indels; std::string alleles; std::vector<char> refbase;
+    DenseResult() {}
+    DenseResult(const DenseResult&) = delete;
+    DenseResult& operator=(const DenseResult&) = delete;
+    ~DenseResult() { free(i); free(f); }
+    bool ensure(size_t need) {
+        if (need <= cap) return true;
+        free(i); free(f);
+        i = (uint32_t*)malloc(need * NI * 4); f = (float*)malloc(need * NF * 4); cap = need;
+        if (!i || !f) { cap = 0; return false; }
+        return true;
+    }
+};
+
 }  // namespace brc
 
 using namespace brc;
@@ -372,12 +387,14 @@ struct XKey { uint64_t key; brc_stat st; };      // a third-allele bucket for th
 struct brc_engine {
     brc_config cfg;
     std::vector<std::string> libs;
-    Backend* be = nullptr;
+    // (declared in this order: what is destroyed last comes first — the staging goes before the backend whose memory it lives in,
+    // the staging stage's threads after both, as brc_destroy always had it)
+    std::unique_ptr<Pool> pool;    // the staging stage's threads (created by the first large batch)
+    std::unique_ptr<Backend> be;
     Staged st;
     Geometry g;
     int state = 0;   // 0 idle, 1 region open, 2 uploaded, 3 computed, 4 fetched
     unsigned format_threads = 0;   // BRC_OPT_FORMAT_THREADS (0: effective_cpus())
-    Pool* pool = nullptr;          // the staging stage's threads (created by the first large batch)
     std::string err;
     // bam_plp_push max-count emulation
     int64_t accepted = 0, n_ext = 0; int32_t last_acc_pos = 0; int32_t last_pos = 0;
@@ -385,13 +402,9 @@ struct brc_engine {
     std::priority_queue<int32_t, std::vector<int32_t>, std::greater<int32_t> > live_ends;
     // fetched result: compact planes from the backend, expanded to the ABI's dense planes
     HostPlanes hp;
-    uint32_t* dense_i = nullptr; float* dense_f = nullptr; size_t dense_cap = 0;
-    std::vector<brc_indel> indels;
-    std::string alleles;
-    std::vector<char> refbase;
+    DenseResult res;
     // brc_fetch_window: the dense result of one window of the computed region (buffers of its own: a fetched whole-region result stays valid)
-    uint32_t* win_i = nullptr; float* win_f = nullptr; size_t win_cap = 0;
-    std::vector<brc_indel> win_indels; std::string win_alleles; std::vector<char> win_refbase; std::vector<XAgg> win_xagg; std::vector<IndelOut> win_iout;
+    DenseResult win; std::vector<XAgg> win_xagg; std::vector<IndelOut> win_iout;
     // BRC_OPT_TEXT_ONLY: the caller only formats (brc_format_region / brc_format_window): no dense planes are built, the
     // formatter reads the compact slot planes; third-allele events are aggregated into a sparse (position, library,
     // bucket)-sorted table instead
@@ -413,7 +426,7 @@ struct brc_engine {
     size_t hint_reads = 0, hint_bases = 0;          // BRC_OPT_EXPECT_*: staging is sized once instead of grown batch by batch
     // formatter state: the text of the last call (one contiguous buffer, capacity kept across calls), the per-chunk
     // buffers the threads format into (kept too: a fresh 300-MB buffer per piece costs more in page faults than the text)
-    char* tbuf = nullptr; size_t tcap = 0, tlen = 0;
+    TextBuf tbuf;
     std::vector<TextBuf> fparts;
     std::vector<const char*> part_ptr; std::vector<size_t> part_len;
     TextBuf wbuf;                                   // brc_format_window's text
@@ -441,7 +454,20 @@ static bool append_big(Pool* pool, HBuf<T>& h, const T* src, size_t k) {
 
 // allele text + std::map<std::string,BasicStat> iteration order (bamreadcount.cpp:323-342, 389-401): the device's reduced indel
 // buckets -> the ABI's list, sorted by (position, library, allele text bytewise)
-static void assemble_indels(const brc_engine* e, const IndelOut* list, int64_t n, std::vector<brc_indel>& out, std::string& alleles) {
+template <class T> static brc_stat stat_of(const T& o) {         // the sums of an IndelOut / XAgg as the ABI's brc_stat
+    brc_stat st;
+    for (int f = 0; f < BRC_NI; ++f) st.i[f] = o.i[f];
+    for (int f = 0; f < BRC_NF; ++f) st.f[f] = o.f[f];
+    return st;
+}
+// a deletion's allele text: '-' and the reference's characters behind the position (bamreadcount.cpp:331-338)
+static std::string deletion_allele(const Geometry& g, const IndelOut& o) {
+    std::string a; a.push_back('-');
+    for (int j = 0; j < -o.len; ++j) { const int64_t p = (int64_t)o.pos + 1 + j; a.push_back((g.ref && p < g.ref_len && g.ref[p]) ? g.ref[p] : 'N'); }
+    return a;
+}
+static void assemble_indels(const brc_engine* e, const IndelOut* list, int64_t n, DenseResult& res) {
+    std::vector<brc_indel>& out = res.indels; std::string& alleles = res.alleles;
     const Geometry& g = e->g; const Staged& s = e->st;
     std::vector<std::string> txt((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
@@ -452,10 +478,7 @@ static void assemble_indels(const brc_engine* e, const IndelOut* list, int64_t n
             const uint8_t* seq = s.seq_at(s.seq_off.p[o.rep_read]);
             const int32_t L = s.l_qseq.p[o.rep_read];
             for (int j = 0; j < o.len; ++j) { const int q = o.rep_qpos + 1 + j; a.push_back(q < L ? "=ACGTN"[canon_bucket(seqi(seq, q))] : 'N'); }
-        } else {
-            a.push_back('-');
-            for (int j = 0; j < -o.len; ++j) { const int64_t p = (int64_t)o.pos + 1 + j; a.push_back((g.ref && p < g.ref_len && g.ref[p]) ? g.ref[p] : 'N'); }
-        }
+        } else a = deletion_allele(g, o);
     }
     std::vector<uint32_t> ord((size_t)n);
     for (size_t i = 0; i < ord.size(); ++i) ord[i] = (uint32_t)i;
@@ -471,8 +494,7 @@ static void assemble_indels(const brc_engine* e, const IndelOut* list, int64_t n
         d.pos = o.pos; d.lib = o.lib; d.len = o.len; d.rep_read = o.rep_read; d.rep_qpos = o.rep_qpos;
         d.allele_off = (uint32_t)alleles.size(); d.allele_len = (uint32_t)txt[ord[i]].size();
         alleles += txt[ord[i]];
-        for (int f = 0; f < BRC_NI; ++f) d.stat.i[f] = o.i[f];
-        for (int f = 0; f < BRC_NF; ++f) d.stat.f[f] = o.f[f];
+        d.stat = stat_of(o);
     }
 }
 
@@ -483,16 +505,10 @@ static void assemble_indels(const brc_engine* e, const IndelOut* list, int64_t n
 // not start from clean queues, the true entries of its lines (format_device_text rewrites them).  Runs inside brc_fetch_result: the
 // reference bases (deletion alleles are the reference's characters, :331-338) are the caller's only until that call returns, and the
 // region before has been formatted by then (include/brc.h, threads), so the queues are what this region will find.
-static std::string deletion_allele(const Geometry& g, const IndelOut& o) {
-    std::string a; a.push_back('-');
-    for (int j = 0; j < -o.len; ++j) { const int64_t p = (int64_t)o.pos + 1 + j; a.push_back((g.ref && p < g.ref_len && g.ref[p]) ? g.ref[p] : 'N'); }
-    return a;
-}
 static void prepare_text_queues(brc_engine* e) {
     const Geometry& g = e->g; const HostPlanes& hp = e->hp; const int Lp = g.Lp;
     e->tail_dels.assign((size_t)Lp, std::vector<QEnt>()); e->tail_pos.assign((size_t)Lp, INT64_MIN);
     for (int64_t i = 0; i < hp.n_indel; ++i) { const IndelOut& o = hp.indel[i]; if (o.len < 0 && o.lib >= 0 && o.lib < Lp && (int64_t)o.pos > e->tail_pos[(size_t)o.lib]) e->tail_pos[(size_t)o.lib] = o.pos; }
-    auto stat_of = [](const IndelOut& o) { brc_stat st; for (int f = 0; f < BRC_NI; ++f) st.i[f] = o.i[f]; for (int f = 0; f < BRC_NF; ++f) st.f[f] = o.f[f]; return st; };
     for (int64_t i = 0; i < hp.n_indel; ++i) {
         const IndelOut& o = hp.indel[i];
         if (o.len >= 0 || o.lib < 0 || o.lib >= Lp || (int64_t)o.pos != e->tail_pos[(size_t)o.lib]) continue;
@@ -548,7 +564,7 @@ int brc_create(const brc_config* cfg, brc_engine** out) {
     e->cfg.lib_names = NULL;
     e->g.Lp = cfg->per_lib ? (cfg->n_libs > 0 ? cfg->n_libs : 1) : 1;
     int err = BRC_OK;
-    e->be = make_backend(e->cfg, &err);
+    e->be.reset(make_backend(e->cfg, &err));
     if (!e->be) { delete e; return err ? err : BRC_E_NODEVICE; }
     e->st.init(e->be->host_alloc());
     e->queue.resize((size_t)e->g.Lp);
@@ -562,9 +578,6 @@ void brc_destroy(brc_engine* e) {
         fprintf(stderr, "engine timing (%lld regions): push %.3f s, upload %.3f s, compute %.3f s, download %.3f s, assemble %.3f s, format %.3f s (of which waiting for the device text %.3f s); third-allele events %llu, indel buckets %llu\n",
                 (long long)e->n_regions, e->t_push, e->t_upload, e->t_compute, e->t_d2h, e->t_post, e->t_format, e->t_textwait, (unsigned long long)e->n_xev_total, (unsigned long long)e->n_indel_total);
     e->st.destroy();
-    delete e->be;
-    free(e->dense_i); free(e->dense_f); free(e->tbuf); free(e->win_i); free(e->win_f);
-    delete e->pool;
     delete e;
 }
 
@@ -602,6 +615,8 @@ int brc_begin_region(brc_engine* e, int32_t tid, int32_t beg0, int32_t end, cons
     return BRC_OK;
 }
 
+}  // extern "C"
+
 // reference length of a CIGAR; -1 when it does not fit 31 bits (a damaged record: positions are int32 everywhere, as in the reference)
 static inline int32_t cigar_rlen(const uint32_t* cig, uint32_t nc, uint64_t* n_indel_ops) {
     int64_t l = 0;
@@ -613,34 +628,125 @@ static inline int32_t cigar_rlen(const uint32_t* cig, uint32_t nc, uint64_t* n_i
     return l > INT32_MAX ? -1 : (int32_t)l;
 }
 
-static int push_reads_staged(brc_engine* e, const brc_read_batch* b, bool* touched, bool pinned);
-
-// A refused batch leaves the staging arrays half appended (per-read arrays and arenas grow before a record is found bad),
-// so the region cannot take further batches: it is abandoned — every later push / upload on it fails with "outside an open
-// region" until the caller opens the next one with brc_begin_region (which resets the staging).
-void* brc_host_alloc(size_t bytes) { return backend_host_alloc(bytes); }
-void brc_host_free(void* p) { if (p) backend_host_free(p); }
 // A mapped read with an M / = / X operator of length zero: htslib's resolve_cigar2 steps ONTO such an operator without asking whether the
 // position lies inside it (it reports the column as a match at the operator's query offset and the deletion behind it one column late).
 // Round 6: such reads are piled up by the cursor itself (brc_core.h: cursor_resolve — walk_pieces / enumerate_indels switch to it).  What
 // stays refused is the one case in which the reference reads memory behind the read: an empty operator reported at the query offset
 // l_qseq (every base of the read already consumed before it).
 static const char* const kEmptyM = "a mapped read has an empty M/=/X CIGAR operator behind its last base (the reference would read past the read's qualities)";
-static int push_reads_any(brc_engine* e, const brc_read_batch* b, bool pinned);
-int brc_push_reads(brc_engine* e, const brc_read_batch* b) { return push_reads_any(e, b, false); }
-int brc_push_reads_pinned(brc_engine* e, const brc_read_batch* b) { return push_reads_any(e, b, true); }
-static int push_reads_any(brc_engine* e, const brc_read_batch* b, bool pinned) {
-    if (!e || !b) return BRC_E_ARG;
-    bool touched = false;
-    int rc;
-    // no exception crosses the C boundary: the parallel staging path allocates (per-chunk tables, the job's std::function), and a C
-    // caller would see std::terminate
-    try { rc = push_reads_staged(e, b, &touched, pinned); }
-    catch (const std::bad_alloc&) { touched = true; rc = fail(e, BRC_E_NOMEM, "host allocation failed while staging reads"); }
-    catch (const std::exception& ex) { touched = true; rc = fail(e, BRC_E_NOMEM, ex.what()); }
-    catch (...) { touched = true; rc = fail(e, BRC_E_NOMEM, "unexpected failure while staging reads"); }
-    if (rc != BRC_OK && touched) e->state = 0;
-    return rc;
+// What a run of reads adds to the region's running quantities — sums, maxima, the extent, the first bad record.  The pooled pass keeps
+// one per chunk of the batch and merges them in file order; the one-thread pass keeps one for the whole batch.
+struct Chunk {
+    uint64_t bq = 0, idp = 0, np = 0;                      // elements of the event-byte rows, indel operators, pieces
+    int32_t max_lq = 0; int64_t max_span = 0, min_pos = INT64_MAX, max_end = INT64_MIN, n_ext = 0, acc = 0;
+    int32_t last_acc_pos = 0; bool empty_m = false, eqx = false;
+    int err = 0; const char* msg = nullptr;                // the chunk's first bad record (its reads behind it are not looked at)
+    uint32_t hist[TABLE_MAX + 1];
+    Chunk() { memset(hist, 0, sizeof hist); }
+};
+struct PushCtx { brc_engine* e; const brc_read_batch* b; size_t n0; uint64_t cb, sb, qb; };      // a batch on its way into the staging: its first read's index there, what its offsets are rebased by
+
+// THE per-read rule of brc_push_reads: read i of the batch (r = n0 + i of the staging; prev: the position of the read before it) is
+// validated, its three offsets rebased, and flag / n_cigar / piece_cnt / wide written; bq_row and iev_off get the read's row LENGTH and
+// indel-operator COUNT (stage_offsets turns them into offsets once the totals in front of the chunk are known).  false: the record is
+// refused, C.err / C.msg say why.  admit(r, pos, end, C) is bam_plp_push's max-count rule for a read the pileup would take: false drops it.
+template <class Admit>
+static inline bool stage_read(const PushCtx& x, size_t i, int32_t prev, Chunk& C, Admit admit) {
+    brc_engine* const e = x.e; Staged& s = e->st; const brc_read_batch* const b = x.b;
+    auto bad = [&](int code, const char* m) { C.err = code; C.msg = m; return false; };
+    const size_t r = x.n0 + i;
+    uint32_t nc = s.n_cigar.p[r];
+    const int32_t lq = s.l_qseq.p[r];
+    if (b->cigar_off[i] + nc > b->n_cigar_total || b->qual_off[i] + (uint64_t)(lq > 0 ? lq : 0) > b->qual_bytes ||
+        b->seq_off[i] + (uint64_t)((lq + 1) / 2) > b->seq_bytes || lq < 0) return bad(BRC_E_ARG, "read offsets outside the batch arenas");
+    if (e->cfg.per_lib && s.lib.p[r] >= e->g.Lp) return bad(BRC_E_ARG, "library index out of range");
+    s.cig_off.p[r] += x.cb; s.seq_off.p[r] += x.sb; s.qual_off.p[r] += x.qb;
+    const uint64_t rowlen = ((uint64_t)lq + 15u) & ~(uint64_t)15u;
+    s.bq_row.p[r] = rowlen; C.bq += rowlen;
+    if (lq <= TABLE_MAX) C.hist[lq]++;
+    if (lq >= (1 << 22)) return bad(BRC_E_LIMIT, "reads of 4 Mbases and more are not supported");
+    if (lq > C.max_lq) C.max_lq = lq;
+    const int32_t pos = s.pos.p[r];
+    if (pos < prev) return bad(BRC_E_ARG, "reads are not coordinate-sorted");
+    uint16_t fl = (uint16_t)(s.flag.p[r] & 0x7fffu);
+    const uint32_t* const cg = s.cigar.p + s.cig_off.p[r];
+    // A record whose CIGAR walks more (or fewer) query bases than it has would send the annotator outside the read's
+    // quality / base rows (htslib indexes the record's memory just the same: undefined there).  Mapped: refused.
+    // Unmapped (some aligners leave the mate's CIGAR on such records; they never reach a column): the CIGAR is dropped.
+    if (lq > 0 && nc > 0) {
+        int64_t ql = 0; bool empty_m = false, eqx = false;
+        for (uint32_t k = 0; k < nc; ++k) { const uint32_t op = cg[k] & 0xfu; if (op == CMATCH || op == CINS || op == CSOFT_CLIP || op == CEQUAL || op == CDIFF) ql += cg[k] >> 4; if (is_mop(op) && (cg[k] >> 4) == 0u) empty_m = true; if (op == CEQUAL || op == CDIFF) eqx = true; }
+        if (ql != lq) {
+            if (!(fl & FUNMAP)) return bad(BRC_E_ARG, "a read's CIGAR and sequence length disagree");
+            nc = 0; s.n_cigar.p[r] = 0;
+        } else if (empty_m && !(fl & FUNMAP)) C.empty_m = true;
+        if (eqx) C.eqx = true;
+    }
+    uint64_t idp = 0;                                     // I / D / P operators of the CIGAR the device will see
+    const int32_t rlen = cigar_rlen(cg, nc, &idp);
+    if (rlen < 0 || (int64_t)pos + rlen > (int64_t)INT32_MAX) {
+        if (!(fl & FUNMAP)) return bad(BRC_E_ARG, "a read ends beyond the last 32-bit position");
+        nc = 0; s.n_cigar.p[r] = 0; idp = 0;
+    }
+    // the read's slots in the raw indel-event list (K1 writes every one of them: an event or an empty mark)
+    s.iev_off.p[r] = (uint32_t)idp; C.idp += idp;
+    // (SEQ "*" on a record that pileup_func would count: the reference takes its bases from whatever follows the empty sequence in the record)
+    if (lq == 0 && nc > 0 && !(fl & (FUNMAP | BRC_NOCOUNT_MASK))) return bad(BRC_E_ARG, "a read without sequence would be counted");
+    const int32_t end = (!(fl & FUNMAP) && nc > 0) ? pos + rlen : pos + 1;           // bam_endpos
+    if (rlen > C.max_span) C.max_span = rlen;
+    if (!(fl & FUNMAP) && pos >= 0) {   // bam_plp_push (htslib 1.10) skips unmapped reads only; region extent: every read it takes (max-count drops included)
+        if (pos < C.min_pos) C.min_pos = pos;
+        if (end > C.max_end) C.max_end = end;
+        C.n_ext++;
+        if (admit(r, pos, end, C)) { C.acc++; C.last_acc_pos = pos; } else fl |= FHOSTDROP;
+    }
+    s.flag.p[r] = fl;
+    // pieces of this read (KB v2): none for a read outside the columns or without a library (-p: it abandons positions instead)
+    const bool entered = read_enters(fl, cg, nc) && pos >= 0 && !(e->cfg.per_lib && s.lib.p[r] < 0);
+    const bool counts = (int)s.mapq.p[r] >= e->cfg.min_mapq && !(fl & BRC_NOCOUNT_MASK);
+    uint32_t np = 0; bool past = false;
+    walk_pieces(e->cfg.insertion_centric != 0, entered, counts, pos, cg, nc, [&](int32_t, int32_t len, int32_t, int qoff, bool) { ++np; if (len > 0 && qoff + len > lq) past = true; });
+    if (past) return bad(BRC_E_ARG, kEmptyM);
+    s.piece_cnt.p[r] = np; C.np += np;
+    s.wide.p[r] = read_has_escape(b->qual + b->qual_off[i], b->seq4 + b->seq_off[i], lq) ? 1 : 0;
+    return true;
+}
+// reads [i0, i1) of the batch, up to the first bad one
+template <class Admit>
+static void stage_chunk(const PushCtx& x, size_t i0, size_t i1, Chunk& C, Admit admit) {
+    const Staged& s = x.e->st;
+    for (size_t i = i0; i < i1; ++i) if (!stage_read(x, i, i == 0 ? x.e->last_pos : s.pos.p[x.n0 + i - 1], C, admit)) return;
+}
+// the chunks' totals join the region's in file order; the first bad record in file order decides the error.  bq0 / idp0: the
+// region's totals in front of every chunk, what stage_offsets starts from.
+static int merge_chunks(brc_engine* e, const Chunk* ch, size_t nch, uint64_t* bq0, uint64_t* idp0) {
+    Staged& s = e->st;
+    for (size_t ci = 0; ci < nch; ++ci) if (ch[ci].err) return fail(e, ch[ci].err, ch[ci].msg);
+    for (size_t ci = 0; ci < nch; ++ci) {
+        const Chunk& C = ch[ci];
+        bq0[ci] = s.bq_elems; idp0[ci] = s.n_indel_ops;
+        s.bq_elems += C.bq; s.n_indel_ops += C.idp;
+        if ((uint64_t)(s.n_pieces += (int64_t)C.np) >= 0xFFFFFFF0ull) return fail(e, BRC_E_LIMIT, "more than 2^32 read segments in one region: split the region");
+        for (int l = 0; l <= TABLE_MAX; ++l) s.len_hist[l] += C.hist[l];
+        if (C.max_lq > s.max_lqseq) s.max_lqseq = C.max_lq;
+        if (C.max_span > s.max_span) s.max_span = C.max_span;
+        if (C.n_ext) {
+            if (e->n_ext == 0) { s.min_pos = C.min_pos; s.max_end = C.max_end; }
+            else { if (C.min_pos < s.min_pos) s.min_pos = C.min_pos; if (C.max_end > s.max_end) s.max_end = C.max_end; }
+            e->n_ext += C.n_ext;
+        }
+        if (C.acc) { e->accepted += C.acc; e->last_acc_pos = C.last_acc_pos; }
+        if (C.empty_m) s.has_empty_m = true;
+        if (C.eqx) s.has_eqx = true;
+    }
+    return BRC_OK;
+}
+// second pass over staged reads [r0, r1): row lengths and indel-operator counts become running offsets
+static void stage_offsets(Staged& s, size_t r0, size_t r1, uint64_t bq, uint64_t idp) {
+    for (size_t r = r0; r < r1; ++r) {
+        const uint64_t len = s.bq_row.p[r]; s.bq_row.p[r] = bq; bq += len;
+        const uint32_t k = s.iev_off.p[r]; s.iev_off.p[r] = (uint32_t)idp; idp += k;
+    }
 }
 
 static int push_reads_staged(brc_engine* e, const brc_read_batch* b, bool* touched, bool pinned) {
@@ -656,236 +762,111 @@ static int push_reads_staged(brc_engine* e, const brc_read_batch* b, bool* touch
     // adopted arenas (brc_push_reads_pinned on a backend that uploads them in place): the region's first push decides for the region
     const bool adopt = pinned && e->be->adopts_arenas();
     if (s.n > 0 && adopt != s.adopted() && (s.seq_total || s.qual_total)) return fail(e, BRC_E_ARG, "a region takes brc_push_reads or brc_push_reads_pinned, not both");
-    const uint64_t cb = s.cigar.n, sb = s.seq_total, qb = s.qual_total;
-    if (e->hint_reads > n0 + n || e->hint_bases > qb + b->qual_bytes) {
-        const size_t hr = std::max(e->hint_reads, n0 + n) + 16, hb = std::max<size_t>(e->hint_bases, qb + b->qual_bytes) + 16;
-        bool okh = s.pos.reserve(hr) && s.flag.reserve(hr) && s.mapq.reserve(hr) && s.l_qseq.reserve(hr) && s.n_cigar.reserve(hr) && s.cig_off.reserve(hr) &&
-                   s.seq_off.reserve(hr) && s.qual_off.reserve(hr) && s.bq_row.reserve(hr) && s.wide.reserve(hr) && s.piece_cnt.reserve(hr) && s.piece_off.reserve(hr) && s.iev_off.reserve(hr) && s.lib.reserve(hr) &&
-                   s.nm.reserve(hr) && s.sm.reserve(hr) && s.tags.reserve(hr) && s.qname_off.reserve(hr) && s.cigar.reserve(hr + hr / 4) &&
-                   (adopt || (s.qual.reserve(hb) && s.seq4.reserve(hb / 2 + hr)));
-        if (!okh) return fail(e, BRC_E_NOMEM, "host staging allocation failed");
+    const PushCtx x = {e, b, n0, s.cigar.n, s.seq_total, s.qual_total};
+    if (e->hint_reads > n0 + n || e->hint_bases > x.qb + b->qual_bytes) {
+        const size_t hr = std::max(e->hint_reads, n0 + n) + 16, hb = std::max<size_t>(e->hint_bases, x.qb + b->qual_bytes) + 16;
+        if (!(s.reserve_reads(hr, hr + hr / 4) && (adopt || (s.qual.reserve(hb) && s.seq4.reserve(hb / 2 + hr))))) return fail(e, BRC_E_NOMEM, "host staging allocation failed");
     }
     // the staging stage's threads (a share of the CPUs the process may use; BRC_OPT_FORMAT_THREADS caps it like the formatter's)
     unsigned pthr = effective_cpus(); if (pthr > 8) pthr = 8;
     if (e->format_threads && e->format_threads < pthr) pthr = e->format_threads;
     const bool par = n >= 8192 && pthr > 1;      // (a stripe of a 1-Mbp piece is 17 000 reads: with the arenas adopted, the per-read pass is what is left of a push)
-    if (par && !e->pool) e->pool = new (std::nothrow) Pool(pthr - 1);
-    Pool* const pool = par ? e->pool : nullptr;
+    if (par && !e->pool) e->pool.reset(new (std::nothrow) Pool(pthr - 1));
+    Pool* const pool = par ? e->pool.get() : nullptr;
     *touched = true;
-    bool ok = s.pos.append(b->pos, n) && s.flag.append(b->flag, n) && s.mapq.append(b->mapq, n) && s.l_qseq.append(b->l_qseq, n) &&
+    bool ok = s.reserve_reads(n0 + n + 16, s.cigar.n + b->n_cigar_total + 16) &&
+              s.pos.append(b->pos, n) && s.flag.append(b->flag, n) && s.mapq.append(b->mapq, n) && s.l_qseq.append(b->l_qseq, n) &&
               s.n_cigar.append(b->n_cigar, n) && s.cig_off.append(b->cigar_off, n) && s.seq_off.append(b->seq_off, n) &&
               s.qual_off.append(b->qual_off, n) && s.cigar.append(b->cigar, b->n_cigar_total) &&
-              (adopt || (append_big(pool, s.seq4, b->seq4, b->seq_bytes) && append_big(pool, s.qual, b->qual, b->qual_bytes))) &&
-              s.bq_row.reserve(n0 + n + 16) && s.wide.reserve(n0 + n + 16) && s.piece_cnt.reserve(n0 + n + 16) && s.piece_off.reserve(n0 + n + 16) && s.iev_off.reserve(n0 + n + 16) && s.lib.reserve(n0 + n + 16) && s.nm.reserve(n0 + n + 16) && s.sm.reserve(n0 + n + 16) && s.tags.reserve(n0 + n + 16);
+              (adopt || (append_big(pool, s.seq4, b->seq4, b->seq_bytes) && append_big(pool, s.qual, b->qual, b->qual_bytes)));
     if (!ok) return fail(e, BRC_E_NOMEM, "host staging allocation failed");
     { uint32_t mx = s.max_ncigar; for (size_t i = 0; i < n; ++i) mx = b->n_cigar[i] > mx ? b->n_cigar[i] : mx; s.max_ncigar = mx; }   // (the engine's wave-form annotator is for reads with five operators and more)
     if (adopt) {
-        if (b->seq_bytes) { Staged::Seg g; g.p = b->seq4; g.off = sb; g.n = b->seq_bytes; s.seq_seg.push_back(g); }
-        if (b->qual_bytes) { Staged::Seg g; g.p = b->qual; g.off = qb; g.n = b->qual_bytes; s.qual_seg.push_back(g); }
+        if (b->seq_bytes) { Staged::Seg g; g.p = b->seq4; g.off = x.sb; g.n = b->seq_bytes; s.seq_seg.push_back(g); }
+        if (b->qual_bytes) { Staged::Seg g; g.p = b->qual; g.off = x.qb; g.n = b->qual_bytes; s.qual_seg.push_back(g); }
     }
-    s.seq_total = sb + b->seq_bytes; s.qual_total = qb + b->qual_bytes;
-    if (!s.qname_off.reserve(n0 + n + 16)) return fail(e, BRC_E_NOMEM, "host staging allocation failed");
+    s.seq_total = x.sb + b->seq_bytes; s.qual_total = x.qb + b->qual_bytes;
     for (size_t i = 0; i < n; ++i) {
         uint64_t off = ~0ull;
         if (b->qname && b->qname[i]) { off = s.qnames.n; if (!s.qnames.append(b->qname[i], strlen(b->qname[i]) + 1)) return fail(e, BRC_E_NOMEM, "host staging allocation failed"); }
         s.qname_off.p[n0 + i] = off;
     }
-    s.qname_off.n = n0 + n;
     for (size_t i = 0; i < n; ++i) {
         s.lib.p[n0 + i] = (e->cfg.per_lib && b->lib) ? b->lib[i] : 0;
         s.nm.p[n0 + i] = b->nm ? b->nm[i] : 0;
         s.sm.p[n0 + i] = b->sm ? b->sm[i] : 0;
         s.tags.p[n0 + i] = b->tags ? b->tags[i] : 0;
     }
-    s.lib.n = s.nm.n = s.sm.n = s.tags.n = s.bq_row.n = s.wide.n = s.piece_cnt.n = s.iev_off.n = n0 + n;
+    s.qname_off.n = s.lib.n = s.nm.n = s.sm.n = s.tags.n = s.bq_row.n = s.wide.n = s.piece_cnt.n = s.iev_off.n = n0 + n;
     const int32_t maxcnt = e->cfg.max_cnt;
-    // ---- large batches: the per-read pass on several threads.  Everything a read contributes to a running quantity — its row
-    // in the event-byte stream, its slots in the raw indel list, its pieces, the region's extent, the length histogram — is a
-    // prefix sum or a reduction: every chunk of reads computes its own, the chunks' totals are scanned, a second pass turns
-    // the per-read lengths into offsets.  The max-count rule (bam_plp_push drops reads that start where the previous one did
-    // once more than -d are buffered) needs its serial state only when the count can be reached at all; the first bad record
-    // in file order decides the error, as in the serial pass.  (One thread staged 6 M reads of a 30-Mbp piece list in 0.15-0.35 s:
-    // the longest stage of the command line's engine thread.)
+    // The per-read pass.  Everything a read contributes to a running quantity — its row in the event-byte stream, its slots in the raw
+    // indel list, its pieces, the region's extent, the length histogram — is a prefix sum or a reduction: every chunk of reads
+    // computes its own (stage_chunk), the chunks' totals are scanned in file order (merge_chunks), a second pass turns the per-read
+    // lengths into offsets (stage_offsets).  Large batches: about four chunks per thread of the pool.  (One thread staged 6 M reads of a
+    // 30-Mbp piece list in 0.15-0.35 s: the longest stage of the command line's engine thread.)
     if (pool && e->accepted + (int64_t)n < (int64_t)maxcnt && !e->heap_built) {
-        struct Chunk {
-            uint64_t bq = 0, idp = 0, np = 0; int32_t max_lq = 0; int64_t max_span = 0; int64_t min_pos = INT64_MAX, max_end = INT64_MIN, n_ext = 0, acc = 0;
-            int32_t last_acc_pos = 0; int err = 0; const char* msg = nullptr; size_t err_at = 0; uint32_t hist[TABLE_MAX + 1]; bool empty_m = false, eqx = false;
-        };
         const size_t CH = (n + (size_t)pool->size() * 4 - 1) / ((size_t)pool->size() * 4);
         const size_t nch = (n + CH - 1) / CH;
-        std::vector<Chunk> ch(nch);
-        pool->run((int64_t)nch, [&](int64_t ci) {
-            Chunk& C = ch[(size_t)ci]; memset(C.hist, 0, sizeof C.hist);
-            const size_t i0 = (size_t)ci * CH, i1 = std::min(n, i0 + CH);
-            auto bad = [&](size_t i, int code, const char* m) { if (!C.err) { C.err = code; C.msg = m; C.err_at = i; } };
-            for (size_t i = i0; i < i1 && !C.err; ++i) {
-                const size_t r = n0 + i;
-                uint32_t nc = s.n_cigar.p[r];
-                if (b->cigar_off[i] + nc > b->n_cigar_total || b->qual_off[i] + (uint64_t)(s.l_qseq.p[r] > 0 ? s.l_qseq.p[r] : 0) > b->qual_bytes ||
-                    b->seq_off[i] + (uint64_t)((s.l_qseq.p[r] + 1) / 2) > b->seq_bytes || s.l_qseq.p[r] < 0) { bad(i, BRC_E_ARG, "read offsets outside the batch arenas"); break; }
-                if (e->cfg.per_lib && s.lib.p[r] >= e->g.Lp) { bad(i, BRC_E_ARG, "library index out of range"); break; }
-                s.cig_off.p[r] += cb; s.seq_off.p[r] += sb; s.qual_off.p[r] += qb;
-                const uint64_t rowlen = ((uint64_t)s.l_qseq.p[r] + 15u) & ~(uint64_t)15u;
-                s.bq_row.p[r] = rowlen; C.bq += rowlen;                                  // (length now, offset in the second pass)
-                if (s.l_qseq.p[r] <= TABLE_MAX) C.hist[s.l_qseq.p[r]]++;
-                if (s.l_qseq.p[r] >= (1 << 22)) { bad(i, BRC_E_LIMIT, "reads of 4 Mbases and more are not supported"); break; }
-                if (s.l_qseq.p[r] > C.max_lq) C.max_lq = s.l_qseq.p[r];
-                const int32_t pos = s.pos.p[r];
-                const int32_t prev = i == 0 ? e->last_pos : s.pos.p[r - 1];
-                if (pos < prev) { bad(i, BRC_E_ARG, "reads are not coordinate-sorted"); break; }
-                const uint16_t fl = (uint16_t)(s.flag.p[r] & 0x7fffu);
-                if (s.l_qseq.p[r] > 0 && nc > 0) {
-                    int64_t ql = 0; bool empty_m = false, eqx = false;
-                    for (uint32_t k = 0; k < nc; ++k) { const uint32_t cg = s.cigar.p[s.cig_off.p[r] + k], op = cg & 0xfu; if (op == CMATCH || op == CINS || op == CSOFT_CLIP || op == CEQUAL || op == CDIFF) ql += cg >> 4; if (is_mop(op) && (cg >> 4) == 0u) empty_m = true; if (op == CEQUAL || op == CDIFF) eqx = true; }
-                    if (ql != s.l_qseq.p[r]) {
-                        if (!(fl & FUNMAP)) { bad(i, BRC_E_ARG, "a read's CIGAR and sequence length disagree"); break; }
-                        nc = 0; s.n_cigar.p[r] = 0;
-                    } else if (empty_m && !(fl & FUNMAP)) C.empty_m = true;
-                    if (eqx) C.eqx = true;
+        std::vector<Chunk> ch(nch); std::vector<uint64_t> bq0(nch), idp0(nch);
+        pool->run((int64_t)nch, [&](int64_t ci) { stage_chunk(x, (size_t)ci * CH, std::min(n, (size_t)ci * CH + CH), ch[(size_t)ci], [](size_t, int32_t, int32_t, const Chunk&) { return true; }); });
+        const int rc = merge_chunks(e, ch.data(), nch, bq0.data(), idp0.data());
+        if (rc) return rc;
+        pool->run((int64_t)nch, [&](int64_t ci) { stage_offsets(s, n0 + (size_t)ci * CH, n0 + std::min(n, (size_t)ci * CH + CH), bq0[(size_t)ci], idp0[(size_t)ci]); });
+    } else {
+        // One chunk on this thread, with the one rule whose state is serial — needed only when the count can be reached at all.
+        // bam_plp_push drops a read when iter->pos == b->core.pos && mempool count > maxcnt: iter->pos equals the start of the last
+        // accepted read; live nodes are accepted reads with end >= pos (lazy removal).
+        Chunk C; uint64_t bq0 = 0, idp0 = 0;
+        stage_chunk(x, 0, n, C, [&](size_t r, int32_t pos, int32_t end, const Chunk& c) {
+            bool take = true;
+            if (e->accepted + c.acc >= maxcnt) {
+                if (!e->heap_built) {
+                    uint64_t dummy = 0;
+                    for (size_t j = 0; j < r; ++j) {
+                        if (s.flag.p[j] & BRC_PUSH_MASK) continue;
+                        const int32_t rl = cigar_rlen(s.cigar.p + s.cig_off.p[j], s.n_cigar.p[j], &dummy);
+                        e->live_ends.push(s.n_cigar.p[j] > 0 ? s.pos.p[j] + rl : s.pos.p[j] + 1);
+                    }
+                    e->heap_built = true;
                 }
-                uint64_t idp = 0;
-                const int32_t rlen = cigar_rlen(s.cigar.p + s.cig_off.p[r], nc, &idp);
-                if (rlen < 0 || (int64_t)s.pos.p[r] + rlen > (int64_t)INT32_MAX) {
-                    if (!(fl & FUNMAP)) { bad(i, BRC_E_ARG, "a read ends beyond the last 32-bit position"); break; }
-                    nc = 0; s.n_cigar.p[r] = 0; idp = 0;
-                }
-                s.iev_off.p[r] = (uint32_t)idp; C.idp += idp;                            // (count now, offset in the second pass)
-                if (s.l_qseq.p[r] == 0 && nc > 0 && !(fl & (FUNMAP | BRC_NOCOUNT_MASK))) { bad(i, BRC_E_ARG, "a read without sequence would be counted"); break; }
-                const int32_t end = (!(fl & FUNMAP) && nc > 0) ? pos + rlen : pos + 1;
-                if (rlen > C.max_span) C.max_span = rlen;
-                const bool accept = !(fl & FUNMAP) && pos >= 0;
-                if (accept) { if (pos < C.min_pos) C.min_pos = pos; if (end > C.max_end) C.max_end = end; C.n_ext++; C.acc++; C.last_acc_pos = pos; }
-                s.flag.p[r] = fl;
-                const uint32_t* cg = s.cigar.p + s.cig_off.p[r];
-                const bool entered = read_enters(fl, cg, nc) && pos >= 0 && !(e->cfg.per_lib && s.lib.p[r] < 0);
-                const bool counts = (int)s.mapq.p[r] >= e->cfg.min_mapq && !(fl & BRC_NOCOUNT_MASK);
-                uint32_t np = 0; bool past = false;
-                const int32_t lq = s.l_qseq.p[r];
-                walk_pieces(e->cfg.insertion_centric != 0, entered, counts, pos, cg, nc, [&](int32_t, int32_t len, int32_t, int qoff, bool) { ++np; if (len > 0 && qoff + len > lq) past = true; });
-                if (past) { bad(i, BRC_E_ARG, kEmptyM); break; }
-                s.piece_cnt.p[r] = np; C.np += np;
-                s.wide.p[r] = read_has_escape(b->qual + b->qual_off[i], b->seq4 + b->seq_off[i], lq) ? 1 : 0;
+                while (!e->live_ends.empty() && e->live_ends.top() < pos) e->live_ends.pop();
+                take = !(pos == (c.acc ? c.last_acc_pos : e->last_acc_pos) && (int64_t)e->live_ends.size() + 1 > (int64_t)maxcnt);
             }
+            if (take && e->heap_built) e->live_ends.push(end);
+            return take;
         });
-        for (size_t ci = 0; ci < nch; ++ci) if (ch[ci].err) return fail(e, ch[ci].err, ch[ci].msg);      // (chunks are in file order: the first bad record's message)
-        // scan of the chunks' totals, then offsets
-        std::vector<uint64_t> bq0(nch), idp0(nch);
-        for (size_t ci = 0; ci < nch; ++ci) {
-            const Chunk& C = ch[ci];
-            bq0[ci] = s.bq_elems; idp0[ci] = s.n_indel_ops;
-            s.bq_elems += C.bq; s.n_indel_ops += C.idp;
-            if ((uint64_t)(s.n_pieces += (int64_t)C.np) >= 0xFFFFFFF0ull) return fail(e, BRC_E_LIMIT, "more than 2^32 read segments in one region: split the region");
-            for (int l = 0; l <= TABLE_MAX; ++l) s.len_hist[l] += C.hist[l];
-            if (C.max_lq > s.max_lqseq) s.max_lqseq = C.max_lq;
-            if (C.max_span > s.max_span) s.max_span = C.max_span;
-            if (C.n_ext) {
-                if (e->n_ext == 0) { s.min_pos = (int64_t)C.min_pos; s.max_end = (int64_t)C.max_end; }
-                else { if (C.min_pos < s.min_pos) s.min_pos = C.min_pos; if (C.max_end > s.max_end) s.max_end = C.max_end; }
-                e->n_ext += C.n_ext;
-            }
-            if (C.acc) { e->accepted += C.acc; e->last_acc_pos = C.last_acc_pos; }
-            if (C.empty_m) s.has_empty_m = true;
-            if (C.eqx) s.has_eqx = true;
-        }
-        pool->run((int64_t)nch, [&](int64_t ci) {
-            uint64_t bq = bq0[(size_t)ci], idp = idp0[(size_t)ci];
-            const size_t i0 = (size_t)ci * CH, i1 = std::min(n, i0 + CH);
-            for (size_t i = i0; i < i1; ++i) {
-                const size_t r = n0 + i;
-                const uint64_t len = s.bq_row.p[r]; s.bq_row.p[r] = bq; bq += len;
-                const uint32_t k = s.iev_off.p[r]; s.iev_off.p[r] = (uint32_t)idp; idp += k;
-            }
-        });
-        e->last_pos = s.pos.p[n0 + n - 1];
-        s.n += (int64_t)n;
-        return BRC_OK;
+        const int rc = merge_chunks(e, &C, 1, &bq0, &idp0);
+        if (rc) return rc;
+        stage_offsets(s, n0, n0 + n, bq0, idp0);
     }
-    for (size_t i = 0; i < n; ++i) {
-        const size_t r = n0 + i;
-        uint32_t nc = s.n_cigar.p[r];
-        if (b->cigar_off[i] + nc > b->n_cigar_total || b->qual_off[i] + (uint64_t)(s.l_qseq.p[r] > 0 ? s.l_qseq.p[r] : 0) > b->qual_bytes ||
-            b->seq_off[i] + (uint64_t)((s.l_qseq.p[r] + 1) / 2) > b->seq_bytes || s.l_qseq.p[r] < 0)
-            return fail(e, BRC_E_ARG, "read offsets outside the batch arenas");
-        if (e->cfg.per_lib && s.lib.p[r] >= e->g.Lp) return fail(e, BRC_E_ARG, "library index out of range");
-        s.cig_off.p[r] += cb; s.seq_off.p[r] += sb; s.qual_off.p[r] += qb;
-        s.bq_row.p[r] = s.bq_elems; s.bq_elems += ((uint64_t)s.l_qseq.p[r] + 15u) & ~(uint64_t)15u;
-        if (s.l_qseq.p[r] <= TABLE_MAX) s.len_hist[s.l_qseq.p[r]]++;
-        if (s.l_qseq.p[r] >= (1 << 22)) return fail(e, BRC_E_LIMIT, "reads of 4 Mbases and more are not supported");
-        if (s.l_qseq.p[r] > s.max_lqseq) s.max_lqseq = s.l_qseq.p[r];
-        const int32_t pos = s.pos.p[r];
-        if (pos < e->last_pos) return fail(e, BRC_E_ARG, "reads are not coordinate-sorted");
-        e->last_pos = pos;
-        uint16_t fl = (uint16_t)(s.flag.p[r] & 0x7fffu);
-        // A record whose CIGAR walks more (or fewer) query bases than it has would send the annotator outside the read's
-        // quality / base rows (htslib indexes the record's memory just the same: undefined there).  Mapped: refused.
-        // Unmapped (some aligners leave the mate's CIGAR on such records; they never reach a column): the CIGAR is dropped.
-        if (s.l_qseq.p[r] > 0 && nc > 0) {
-            int64_t ql = 0; bool empty_m = false, eqx = false;
-            for (uint32_t k = 0; k < nc; ++k) { const uint32_t cg = s.cigar.p[s.cig_off.p[r] + k], op = cg & 0xfu; if (op == CMATCH || op == CINS || op == CSOFT_CLIP || op == CEQUAL || op == CDIFF) ql += cg >> 4; if (is_mop(op) && (cg >> 4) == 0u) empty_m = true; if (op == CEQUAL || op == CDIFF) eqx = true; }
-            if (ql != s.l_qseq.p[r]) {
-                if (!(fl & FUNMAP)) return fail(e, BRC_E_ARG, "a read's CIGAR and sequence length disagree");
-                nc = 0; s.n_cigar.p[r] = 0;
-            } else if (empty_m && !(fl & FUNMAP)) s.has_empty_m = true;
-            if (eqx) s.has_eqx = true;
-        }
-        uint64_t idp = 0;                                     // I / D / P operators of the CIGAR the device will see
-        const int32_t rlen = cigar_rlen(s.cigar.p + s.cig_off.p[r], nc, &idp);
-        if (rlen < 0 || (int64_t)s.pos.p[r] + rlen > (int64_t)INT32_MAX) {
-            if (!(fl & FUNMAP)) return fail(e, BRC_E_ARG, "a read ends beyond the last 32-bit position");
-            nc = 0; s.n_cigar.p[r] = 0; idp = 0;
-        }
-        // the read's slots in the raw indel-event list (K1 writes every one of them: an event or an empty mark)
-        s.iev_off.p[r] = (uint32_t)s.n_indel_ops; s.n_indel_ops += idp;
-        if (s.l_qseq.p[r] == 0 && nc > 0 && !(fl & (FUNMAP | BRC_NOCOUNT_MASK))) {
-            // (SEQ "*" on a record that pileup_func would count: the reference takes its bases from whatever follows the
-            // empty sequence in the record)
-            return fail(e, BRC_E_ARG, "a read without sequence would be counted");
-        }
-        const int32_t end = (!(fl & FUNMAP) && nc > 0) ? pos + rlen : pos + 1;           // bam_endpos
-        if (rlen > s.max_span) s.max_span = rlen;
-        bool accept = !(fl & FUNMAP) && pos >= 0;      // bam_plp_push (htslib 1.10) skips unmapped reads only
-        if (accept) {   // region extent: every read bam_plp_push takes (max-count drops included)
-            if (e->n_ext == 0) { s.min_pos = pos; s.max_end = end; }
-            else { if (pos < s.min_pos) s.min_pos = pos; if (end > s.max_end) s.max_end = end; }
-            e->n_ext++;
-        }
-        if (accept && e->accepted >= maxcnt) {
-            // bam_plp_push: drop when iter->pos == b->core.pos && mempool count > maxcnt.  iter->pos equals the
-            // start of the last accepted read; live nodes are accepted reads with end >= pos (lazy removal).
-            if (!e->heap_built) {
-                uint64_t dummy = 0;
-                for (size_t j = 0; j < r; ++j) {
-                    const uint16_t f2 = s.flag.p[j];
-                    if (f2 & BRC_PUSH_MASK) continue;
-                    const int32_t rl = cigar_rlen(s.cigar.p + s.cig_off.p[j], s.n_cigar.p[j], &dummy);
-                    e->live_ends.push(s.n_cigar.p[j] > 0 ? s.pos.p[j] + rl : s.pos.p[j] + 1);
-                }
-                e->heap_built = true;
-            }
-            while (!e->live_ends.empty() && e->live_ends.top() < pos) e->live_ends.pop();
-            if (pos == e->last_acc_pos && (int64_t)e->live_ends.size() + 1 > (int64_t)maxcnt) { accept = false; fl |= FHOSTDROP; }
-        }
-        s.flag.p[r] = fl;
-        if (accept) {
-            e->accepted++; e->last_acc_pos = pos;
-            if (e->heap_built) e->live_ends.push(end);
-        }
-        {   // pieces of this read (KB v2): none for a read outside the columns or without a library (-p: it abandons positions instead)
-            const uint32_t* cg = s.cigar.p + s.cig_off.p[r];
-            const bool entered = read_enters(fl, cg, nc) && pos >= 0 && !(e->cfg.per_lib && s.lib.p[r] < 0);
-            const bool counts = (int)s.mapq.p[r] >= e->cfg.min_mapq && !(fl & BRC_NOCOUNT_MASK);
-            uint32_t np = 0; bool past = false;
-            const int32_t lq = s.l_qseq.p[r];
-            walk_pieces(e->cfg.insertion_centric != 0, entered, counts, pos, cg, nc, [&](int32_t, int32_t len, int32_t, int qoff, bool) { ++np; if (len > 0 && qoff + len > lq) past = true; });
-            if (past) return fail(e, BRC_E_ARG, kEmptyM);
-            s.piece_cnt.p[r] = np;
-            if ((uint64_t)(s.n_pieces += np) >= 0xFFFFFFF0ull) return fail(e, BRC_E_LIMIT, "more than 2^32 read segments in one region: split the region");
-            s.wide.p[r] = read_has_escape(b->qual + b->qual_off[i], b->seq4 + b->seq_off[i], lq) ? 1 : 0;
-        }
-    }
+    if (n) e->last_pos = s.pos.p[n0 + n - 1];
     s.n += (int64_t)n;
     return BRC_OK;
 }
+
+// A refused batch leaves the staging arrays half appended (per-read arrays and arenas grow before a record is found bad),
+// so the region cannot take further batches: it is abandoned — every later push / upload on it fails with "outside an open
+// region" until the caller opens the next one with brc_begin_region (which resets the staging).
+static int push_reads_any(brc_engine* e, const brc_read_batch* b, bool pinned) {
+    if (!e || !b) return BRC_E_ARG;
+    bool touched = false;
+    int rc;
+    // no exception crosses the C boundary: the parallel staging path allocates (per-chunk tables, the job's std::function), and a C
+    // caller would see std::terminate
+    try { rc = push_reads_staged(e, b, &touched, pinned); }
+    catch (const std::bad_alloc&) { touched = true; rc = fail(e, BRC_E_NOMEM, "host allocation failed while staging reads"); }
+    catch (const std::exception& ex) { touched = true; rc = fail(e, BRC_E_NOMEM, ex.what()); }
+    catch (...) { touched = true; rc = fail(e, BRC_E_NOMEM, "unexpected failure while staging reads"); }
+    if (rc != BRC_OK && touched) e->state = 0;
+    return rc;
+}
+
+extern "C" {
+
+void* brc_host_alloc(size_t bytes) { return backend_host_alloc(bytes); }
+void brc_host_free(void* p) { if (p) backend_host_free(p); }
+int brc_push_reads(brc_engine* e, const brc_read_batch* b) { return push_reads_any(e, b, false); }
+int brc_push_reads_pinned(brc_engine* e, const brc_read_batch* b) { return push_reads_any(e, b, true); }
 
 int brc_upload(brc_engine* e) {
     if (!e) return BRC_E_ARG;
@@ -935,6 +916,31 @@ static int compute_passes(brc_engine* e, int32_t n, brc_timing* t) {
     return BRC_OK;
 }
 
+// column 3: the raw reference characters of [pos0, pos0 + n) (bamreadcount.cpp:353), 'N' where the reference has none
+static void fill_refbase(const Geometry& g, int64_t pos0, int64_t n, std::vector<char>& out) {
+    out.resize((size_t)n + 1);
+    const int64_t have = g.ref ? std::max<int64_t>(0, std::min<int64_t>(n, g.ref_len - pos0)) : 0;
+    if (have) memcpy(out.data(), g.ref + pos0, (size_t)have);
+    for (int64_t k = 0; k < have; ++k) if (!out[(size_t)k]) out[(size_t)k] = 'N';
+    if (n > have) memset(out.data() + have, 'N', (size_t)(n - have));
+}
+// the slot planes of hp (n positions, `stride` apart) -> the dense planes of d
+static int expand_dense(brc_engine* e, DenseResult& d, const HostPlanes& hp, int64_t n, int64_t stride) {
+    if (!d.ensure((size_t)e->g.Lp * NBUCKET * (size_t)stride + 16)) return fail(e, BRC_E_NOMEM, "host allocation of the dense planes failed");
+    expand_slots(hp, e->g.Lp, n, stride, d.i, d.f);
+    return BRC_OK;
+}
+// the fields of a brc_result that describes positions [pos0, pos0 + n) with the planes of hp and the dense result d
+static void fill_result(const brc_engine* e, brc_result* out, int32_t beg0, int32_t end, int32_t pos0, int64_t n, int64_t stride, const HostPlanes& hp, const DenseResult& d) {
+    memset(out, 0, sizeof *out);
+    out->tid = e->g.tid; out->beg0 = beg0; out->end = end; out->pos0 = pos0; out->n_pos = n; out->stride = stride; out->n_lib = e->g.Lp;
+    out->ncol = hp.ncol; out->depth = hp.depth; out->istat = d.i; out->fstat = d.f;
+    out->unavail = e->cfg.per_lib ? hp.unavail : NULL;
+    out->refbase = d.refbase.data();
+    out->n_indel = (int64_t)d.indels.size(); out->indel = d.indels.data();
+    out->alleles = d.alleles.data(); out->alleles_len = d.alleles.size();
+}
+
 int brc_fetch_result(brc_engine* e, brc_result* out) {
     if (!e || !out) return BRC_E_ARG;
     if (e->state < 3) return fail(e, BRC_E_ARG, "brc_fetch_result before brc_compute");
@@ -945,51 +951,28 @@ int brc_fetch_result(brc_engine* e, brc_result* out) {
     if (rc) return fail(e, rc, e->be->last_error());
     const double t_dl = now_s(); e->t_d2h += t_dl - t_in;
     e->n_xev_total += e->hp.n_xagg; e->n_indel_total += (uint64_t)e->hp.n_indel;
-    const Geometry& g = e->g; const HostPlanes& hp = e->hp;
-    // column 3: raw reference character (bamreadcount.cpp:353)
-    e->refbase.resize((size_t)g.P + 1);
-    if (!e->text_result) {
-        const int64_t have = g.ref ? std::max<int64_t>(0, std::min<int64_t>(g.P, g.ref_len - g.pos0)) : 0;
-        if (have) memcpy(e->refbase.data(), g.ref + g.pos0, (size_t)have);
-        for (int64_t k = 0; k < have; ++k) if (!e->refbase[(size_t)k]) e->refbase[(size_t)k] = 'N';
-        if (g.P > have) memset(e->refbase.data() + have, 'N', (size_t)(g.P - have));
-    }
-    // a text result leaves the indel buckets to the device's lines; the host keeps what its deletion queues need (prepare_text_queues)
-    if (e->text_result) { e->indels.clear(); e->alleles.clear(); prepare_text_queues(e); }
-    else assemble_indels(e, hp.indel, hp.n_indel, e->indels, e->alleles);
-    memset(out, 0, sizeof *out);
-    out->tid = g.tid; out->beg0 = g.beg0; out->end = g.end; out->pos0 = g.pos0; out->n_pos = g.P; out->stride = g.PS; out->n_lib = g.Lp;
+    const Geometry& g = e->g; const HostPlanes& hp = e->hp; DenseResult& d = e->res;
     if (e->text_result) {
-    } else if (e->text_only) {
-        // third-allele buckets -> sorted by (position, library, bucket) for the formatter's merge (the device groups them by tile and library)
-        e->xagg.clear(); e->xagg.reserve((size_t)hp.n_xagg);
-        for (uint64_t i = 0; i < hp.n_xagg; ++i) {
-            const XAgg& x = hp.xagg[i];
-            if ((int64_t)(x.lib_b >> 8) >= g.Lp || (x.lib_b & 0xffu) >= (uint32_t)NBUCKET || (int64_t)x.k >= g.P) continue;
-            XKey a; a.key = ((uint64_t)x.k << 16) | (uint64_t)(x.lib_b & 0xffffu);
-            for (int f = 0; f < BRC_NI; ++f) a.st.i[f] = x.i[f];
-            for (int f = 0; f < BRC_NF; ++f) a.st.f[f] = x.f[f];
-            e->xagg.push_back(a);
-        }
-        std::sort(e->xagg.begin(), e->xagg.end(), [](const XKey& a, const XKey& b) { return a.key < b.key; });
+        // a text result leaves the indel buckets to the device's lines; the host keeps what its deletion queues need (prepare_text_queues)
+        d.indels.clear(); d.alleles.clear(); prepare_text_queues(e);
     } else {
-        const size_t need = (size_t)g.Lp * NBUCKET * (size_t)g.PS + 16;
-        if (need > e->dense_cap) {
-            free(e->dense_i); free(e->dense_f);
-            e->dense_i = (uint32_t*)malloc(need * NI * 4); e->dense_f = (float*)malloc(need * NF * 4); e->dense_cap = need;
-            if (!e->dense_i || !e->dense_f) { e->dense_cap = 0; return fail(e, BRC_E_NOMEM, "host allocation of the dense planes failed"); }
-        }
-        expand_slots(hp, g.Lp, g.P, g.PS, e->dense_i, e->dense_f);
+        fill_refbase(g, g.pos0, g.P, d.refbase);
+        assemble_indels(e, hp.indel, hp.n_indel, d);
+        if (e->text_only) {
+            // third-allele buckets -> sorted by (position, library, bucket) for the formatter's merge (the device groups them by tile and library)
+            e->xagg.clear(); e->xagg.reserve((size_t)hp.n_xagg);
+            for (uint64_t i = 0; i < hp.n_xagg; ++i) {
+                const XAgg& x = hp.xagg[i];
+                if ((int64_t)(x.lib_b >> 8) >= g.Lp || (x.lib_b & 0xffu) >= (uint32_t)NBUCKET || (int64_t)x.k >= g.P) continue;
+                XKey a; a.key = ((uint64_t)x.k << 16) | (uint64_t)(x.lib_b & 0xffffu); a.st = stat_of(x);
+                e->xagg.push_back(a);
+            }
+            std::sort(e->xagg.begin(), e->xagg.end(), [](const XKey& a, const XKey& b) { return a.key < b.key; });
+        } else if ((rc = expand_dense(e, d, hp, g.P, g.PS)) != BRC_OK) return rc;
     }
-    out->ncol = hp.ncol; out->depth = hp.depth;
-    out->istat = e->text_only ? NULL : e->dense_i; out->fstat = e->text_only ? NULL : e->dense_f;
-    out->unavail = e->cfg.per_lib ? hp.unavail : NULL;
-    out->refbase = e->refbase.data();
-    if (e->text_result) {
-        out->ncol = out->depth = out->unavail = NULL; out->refbase = NULL;
-    }
-    out->n_indel = (int64_t)e->indels.size(); out->indel = e->indels.data();
-    out->alleles = e->alleles.data(); out->alleles_len = e->alleles.size();
+    fill_result(e, out, g.beg0, g.end, g.pos0, g.P, g.PS, hp, d);
+    if (e->text_only) { out->istat = NULL; out->fstat = NULL; }
+    if (e->text_result) { out->ncol = out->depth = out->unavail = NULL; out->refbase = NULL; }
     out->n_events = hp.n_events;
     for (int w = 0; w < BRC_N_WARN; ++w) out->warn[w] = hp.warn[w];
     e->state = 4; e->t_post += now_s() - t_dl;
@@ -1017,28 +1000,11 @@ int brc_fetch_window(brc_engine* e, int32_t beg0, int32_t end, brc_result* out) 
     for (uint64_t i = 0; i < hw.n_xagg; ++i) { const XAgg& x = hw.xagg[i]; if ((int64_t)x.k >= k0 && (int64_t)x.k < k1) { XAgg y = x; y.k = (uint32_t)((int64_t)x.k - k0); e->win_xagg.push_back(y); } }
     for (int64_t i = 0; i < hw.n_indel; ++i) { const IndelOut& o = hw.indel[i]; if (o.pos >= wpos0 && (int64_t)o.pos < (int64_t)wpos0 + n) e->win_iout.push_back(o); }
     hw.xagg = e->win_xagg.data(); hw.n_xagg = e->win_xagg.size();
-    assemble_indels(e, e->win_iout.data(), (int64_t)e->win_iout.size(), e->win_indels, e->win_alleles);
-    const size_t need = (size_t)g.Lp * NBUCKET * (size_t)WS + 16;
-    if (need > e->win_cap) {
-        free(e->win_i); free(e->win_f);
-        e->win_i = (uint32_t*)malloc(need * NI * 4); e->win_f = (float*)malloc(need * NF * 4); e->win_cap = need;
-        if (!e->win_i || !e->win_f) { e->win_cap = 0; return fail(e, BRC_E_NOMEM, "host allocation of the dense planes failed"); }
-    }
-    expand_slots(hw, g.Lp, n, WS, e->win_i, e->win_f);
-    e->win_refbase.resize((size_t)n + 1);
-    {
-        const int64_t have = g.ref ? std::max<int64_t>(0, std::min<int64_t>(n, g.ref_len - wpos0)) : 0;
-        if (have) memcpy(e->win_refbase.data(), g.ref + wpos0, (size_t)have);
-        for (int64_t k = 0; k < have; ++k) if (!e->win_refbase[(size_t)k]) e->win_refbase[(size_t)k] = 'N';
-        if (n > have) memset(e->win_refbase.data() + have, 'N', (size_t)(n - have));
-    }
-    memset(out, 0, sizeof *out);
-    out->tid = g.tid; out->beg0 = beg0; out->end = end; out->pos0 = wpos0; out->n_pos = n; out->stride = WS; out->n_lib = g.Lp;
-    out->ncol = hw.ncol; out->depth = hw.depth; out->istat = e->win_i; out->fstat = e->win_f;
-    out->unavail = e->cfg.per_lib ? hw.unavail : NULL;
-    out->refbase = e->win_refbase.data();
-    out->n_indel = (int64_t)e->win_indels.size(); out->indel = e->win_indels.data();
-    out->alleles = e->win_alleles.data(); out->alleles_len = e->win_alleles.size();
+    DenseResult& d = e->win;
+    assemble_indels(e, e->win_iout.data(), (int64_t)e->win_iout.size(), d);
+    if ((rc = expand_dense(e, d, hw, n, WS)) != BRC_OK) return rc;
+    fill_refbase(g, wpos0, n, d.refbase);
+    fill_result(e, out, beg0, end, wpos0, n, WS, hw, d);
     // events of the window: its pileup columns inside [beg0, end), abandoned positions left out as the device counts them
     uint64_t ev = 0;
     for (int l = 0; l < g.Lp; ++l) for (int64_t k = 0; k < n; ++k) {
@@ -1106,6 +1072,31 @@ int brc_clear_indel_queue(brc_engine* e) {
     return BRC_OK;
 }
 
+}  // extern "C"
+
+// IndelQueue::process (IndelQueue.cpp:3-15) at (tid, pos): stale entries are dropped from the FRONT only, then the run of entries due
+// here is handed to on_entry (false: out of memory, stop) and taken — an entry behind one that is due later stays where it is
+template <class F>
+static bool queue_due(std::deque<QEnt>& q, uint32_t tid, int32_t pos, F on_entry) {
+    while (!q.empty() && (q.front().tid != tid || q.front().pos < (uint32_t)pos)) q.pop_front();
+    for (; !q.empty() && q.front().tid == tid && q.front().pos == (uint32_t)pos; q.pop_front()) if (!on_entry(q.front())) return false;
+    return true;
+}
+// the look-ahead of the same: the read counts queue_due will hand out at (tid, pos), the queue left as it is (they join the depth
+// column, which is printed in front of the entries: IndelQueue.cpp:11, bamreadcount.cpp:415)
+static uint32_t queue_due_depth(const std::deque<QEnt>& q, uint32_t tid, int32_t pos) {
+    uint32_t n = 0; bool taking = false;
+    for (const QEnt& x : q) {
+        const bool stale = x.tid != tid || x.pos < (uint32_t)pos;
+        if (!taking && stale) continue;
+        if (x.tid != tid || x.pos != (uint32_t)pos) break;
+        taking = true; n += x.st.i[I_N];
+    }
+    return n;
+}
+
+extern "C" {
+
 // Record assembly for plane indices [k0,k1) into `out`, with deletion queues `queue` (one FIFO per library).
 // Lines are printed for positions inside [wbeg0, wend) with coordinate pos + 1 - delta.  Returns false when memory ran out.
 static bool format_range(const brc_engine* e, const brc_result* r, const char* chrom, int64_t k0, int64_t k1,
@@ -1145,19 +1136,7 @@ static bool format_range(const brc_engine* e, const brc_result* r, const char* c
         if (tot == 0) continue;                                                           // no reads: no pileup callback
         // deletions queued for this position add their read counts to the depth column (IndelQueue.cpp:11, :415); only
         // the libraries present in the column look at their queue (:360-411)
-        for (int l = 0; l < Lp; ++l) {
-            const std::deque<QEnt>& q = queue[(size_t)l];
-            if (q.empty() || r->ncol[(int64_t)l * S + k] == 0) continue;
-            // exactly IndelQueue::process: stale entries are dropped from the FRONT only, then the run of entries due here
-            // is taken — an entry behind one that is due later (or behind a stale one that follows a due one) stays
-            bool taking = false;
-            for (const QEnt& x : q) {
-                const bool stale = x.tid != tid || x.pos < (uint32_t)pos;
-                if (!taking && stale) continue;
-                if (x.tid != tid || x.pos != (uint32_t)pos) break;
-                taking = true; depth += x.st.i[I_N];
-            }
-        }
+        for (int l = 0; l < Lp; ++l) if (r->ncol[(int64_t)l * S + k] != 0) depth += queue_due_depth(queue[(size_t)l], tid, pos);
         const size_t line_start = out.n;
         char* w = out.room(line0);
         if (!w) return false;
@@ -1216,13 +1195,7 @@ static bool format_range(const brc_engine* e, const brc_result* r, const char* c
                     queue[(size_t)l].push_back(q);
                 } else if (!entry(r->alleles + d.allele_off, d.allele_len, d.stat.i, d.stat.f)) return false;   // :399
             }
-            // IndelQueue::process (IndelQueue.cpp:3-15)
-            std::deque<QEnt>& q = queue[(size_t)l];
-            while (!q.empty() && ((q.front().tid == tid && q.front().pos < (uint32_t)pos) || q.front().tid != tid)) q.pop_front();
-            while (!q.empty() && q.front().tid == tid && q.front().pos == (uint32_t)pos) {
-                if (!entry(q.front().allele.data(), q.front().allele.size(), q.front().st.i, q.front().st.f)) return false;
-                q.pop_front();
-            }
+            if (!queue_due(queue[(size_t)l], tid, pos, [&](const QEnt& x) { return entry(x.allele.data(), x.allele.size(), x.st.i, x.st.f); })) return false;
             if (per_lib) { *w++ = '\t'; *w++ = '}'; }
         }
         *w++ = '\n';
@@ -1350,14 +1323,7 @@ static int format_device_text(brc_engine* e, const brc_result* r) {
                 QEnt q; q.tid = tid; q.pos = (uint32_t)pos + 1; q.st = dels[di].st; q.allele = dels[di].allele;
                 queue[(size_t)l].push_back(q);
             }
-            std::deque<QEnt>& q = queue[(size_t)l];                                       // IndelQueue::process
-            while (!q.empty() && ((q.front().tid == tid && q.front().pos < (uint32_t)pos) || q.front().tid != tid)) q.pop_front();
-            while (!q.empty() && q.front().tid == tid && q.front().pos == (uint32_t)pos) {
-                if (!entry(q.front().allele.data(), q.front().allele.size(), q.front().st.i, q.front().st.f)) return false;
-                extra += q.front().st.i[I_N];
-                q.pop_front();
-            }
-            return true;
+            return queue_due(queue[(size_t)l], tid, pos, [&](const QEnt& x) { extra += x.st.i[I_N]; return entry(x.allele.data(), x.allele.size(), x.st.i, x.st.f); });
         };
         bool ok = true;
         if (!per_lib) ok = block_tokens(L1) && lib_tail(0);
@@ -1440,58 +1406,52 @@ static int format_chunks(brc_engine* e, const brc_result* r, const char* chrom, 
     return BRC_OK;
 }
 
+// the chunks' buffers as the parts of a host-formatted region (e->part_ptr / e->part_len, as format_device_text leaves them for its route)
+static void chunk_parts(brc_engine* e, int64_t nch) {
+    e->part_ptr.resize((size_t)nch); e->part_len.resize((size_t)nch);
+    for (int64_t c = 0; c < nch; ++c) { e->part_ptr[(size_t)c] = e->fparts[(size_t)c].p ? e->fparts[(size_t)c].p : ""; e->part_len[(size_t)c] = e->fparts[(size_t)c].n; }
+}
+// one contiguous text: every part is copied to its offset in e->tbuf by up to nthr threads (the buffer keeps its capacity across calls)
+static int concat_parts(brc_engine* e, unsigned nthr, const char** text, size_t* text_len) {
+    const size_t np = e->part_len.size();
+    std::vector<size_t> off(np + 1, 0);
+    for (size_t i = 0; i < np; ++i) off[i + 1] = off[i] + e->part_len[i];
+    TextBuf& t = e->tbuf; t.clear();
+    if (!t.room(off[np] + 1)) return fail(e, BRC_E_NOMEM, "host allocation of the text buffer failed");
+    parallel_for((int64_t)np, nthr, [&](int64_t i) { if (e->part_len[(size_t)i]) memcpy(t.p + off[(size_t)i], e->part_ptr[(size_t)i], e->part_len[(size_t)i]); });
+    t.n = off[np]; t.p[t.n] = 0;
+    *text = t.p;
+    if (text_len) *text_len = t.n;
+    return BRC_OK;
+}
+// both routes to a region's text leave it as e->part_ptr / e->part_len: the device's lines with the host's patches between them, or
+// the chunks the host formatted
+static int format_parts(brc_engine* e, const brc_result* r, const char* chrom, unsigned* threads) {
+    *threads = 1;
+    if (r->ncol == NULL && e->text_result) return format_device_text(e, r);
+    int64_t nch = 0;
+    const int rc = format_chunks(e, r, chrom, &nch, threads);
+    if (rc == BRC_OK) chunk_parts(e, nch);
+    return rc;
+}
+
 int brc_format_region(brc_engine* e, const brc_result* r, const char* chrom, const char** text, size_t* text_len) {
     if (!e || !r || !chrom || !text) return BRC_E_ARG;
     const double t_in = now_s();
-    if (r->ncol == NULL && e->text_result) {                       // device text: concatenate the pieces
-        const int rc0 = format_device_text(e, r);
-        if (rc0) return rc0;
-        size_t total = 0; for (size_t v : e->part_len) total += v;
-        if (total + 1 > e->tcap) {
-            free(e->tbuf); e->tcap = total + total / 4 + 4096; e->tbuf = (char*)malloc(e->tcap);
-            if (!e->tbuf) { e->tcap = 0; return fail(e, BRC_E_NOMEM, "host allocation of the text buffer failed"); }
-        }
-        size_t at = 0; for (size_t i = 0; i < e->part_len.size(); ++i) { memcpy(e->tbuf + at, e->part_ptr[i], e->part_len[i]); at += e->part_len[i]; }
-        e->tbuf[total] = 0; e->tlen = total; *text = e->tbuf; if (text_len) *text_len = total;
-        e->t_format += now_s() - t_in;
-        return BRC_OK;
-    }
-    int64_t nch = 0; unsigned nthr = 1;
-    const int rc = format_chunks(e, r, chrom, &nch, &nthr);
-    if (rc) return rc;
-    std::vector<TextBuf>& parts = e->fparts;
-    // one contiguous text: every chunk is copied to its offset by the pool (the buffer keeps its capacity across calls)
-    std::vector<size_t> off((size_t)nch + 1, 0);
-    for (int64_t c = 0; c < nch; ++c) off[(size_t)c + 1] = off[(size_t)c] + parts[(size_t)c].n;
-    const size_t total = off[(size_t)nch];
-    if (total + 1 > e->tcap) {
-        free(e->tbuf); e->tcap = total + total / 4 + 4096; e->tbuf = (char*)malloc(e->tcap);
-        if (!e->tbuf) { e->tcap = 0; return fail(e, BRC_E_NOMEM, "host allocation of the text buffer failed"); }
-    }
-    parallel_for(nch, nthr, [&](int64_t c) { if (parts[(size_t)c].n) memcpy(e->tbuf + off[(size_t)c], parts[(size_t)c].p, parts[(size_t)c].n); });
-    e->tbuf[total] = 0; e->tlen = total;
-    *text = e->tbuf;
-    if (text_len) *text_len = total;
-    e->t_format += now_s() - t_in;
-    return BRC_OK;
+    unsigned nthr = 1;
+    int rc = format_parts(e, r, chrom, &nthr);
+    if (rc == BRC_OK) rc = concat_parts(e, nthr, text, text_len);
+    if (rc == BRC_OK) e->t_format += now_s() - t_in;
+    return rc;
 }
 
 int brc_format_region_parts(brc_engine* e, const brc_result* r, const char* chrom, const char* const** parts, const size_t** part_lens, size_t* n_parts) {
     if (!e || !r || !chrom || !parts || !part_lens || !n_parts) return BRC_E_ARG;
     const double t_in = now_s();
-    if (r->ncol == NULL && e->text_result) {
-        const int rc0 = format_device_text(e, r);
-        if (rc0) return rc0;
-        *parts = e->part_ptr.data(); *part_lens = e->part_len.data(); *n_parts = e->part_ptr.size();
-        e->t_format += now_s() - t_in;
-        return BRC_OK;
-    }
-    int64_t nch = 0; unsigned nthr = 1;
-    const int rc = format_chunks(e, r, chrom, &nch, &nthr);
+    unsigned nthr = 1;
+    const int rc = format_parts(e, r, chrom, &nthr);
     if (rc) return rc;
-    e->part_ptr.resize((size_t)nch); e->part_len.resize((size_t)nch);
-    for (int64_t c = 0; c < nch; ++c) { e->part_ptr[(size_t)c] = e->fparts[(size_t)c].p ? e->fparts[(size_t)c].p : ""; e->part_len[(size_t)c] = e->fparts[(size_t)c].n; }
-    *parts = e->part_ptr.data(); *part_lens = e->part_len.data(); *n_parts = (size_t)nch;
+    *parts = e->part_ptr.data(); *part_lens = e->part_len.data(); *n_parts = e->part_ptr.size();
     e->t_format += now_s() - t_in;
     return BRC_OK;
 }

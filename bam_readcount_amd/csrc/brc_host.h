@@ -102,6 +102,14 @@ struct Staged {
     // per 64-position tile of the planes [pos0, pos0 + P): TILE_UNWANTED, or the first and last lane any window [beg - 1, end) asks
     // for (lo | hi << 8) — the tile is piled up for those lanes only (empty vector: no hint, everything is wanted)
     std::vector<uint16_t> wanted_tiles(int32_t pos0, int64_t P) const;
+    // every HBuf above, named ONCE: the per-read arrays (one element per staged read), then the arenas.  init / clear / destroy and the
+    // reservations go through these two — a new buffer is its declaration and its name here
+    template <class F> void each_read_buf(F f) {
+        f(pos); f(flag); f(mapq); f(lib); f(l_qseq); f(n_cigar); f(cig_off); f(seq_off); f(qual_off); f(nm); f(sm); f(tags);
+        f(bq_row); f(wide); f(piece_cnt); f(piece_off); f(iev_off); f(qname_off);
+    }
+    template <class F> void each_buf(F f) { each_read_buf(f); f(cigar); f(seq4); f(qual); f(qnames); }
+    bool reserve_reads(size_t reads, size_t cigar_ops);      // room in every per-read array and for the CIGAR operators
     void init(const HostAlloc* A);
     void clear();
     void destroy();

@@ -139,13 +139,33 @@ def test_large_batches_are_staged_on_several_threads_like_on_one(sim_lib, oracle
     eng = capi.Engine(sim_lib, per_lib=True, insertion_centric=True, lib_names=names)
     eng.begin_region(0, 0, 120_000, ref); eng.push_reads(capi.select_reads(arrs, np.arange(half))); eng.push_reads(capi.select_reads(arrs, np.arange(half, len(arrs["pos"]))))
     parity.assert_results_equal(eng.end_region(), r1, "two pooled batches"); assert eng.format_region("chrS") == t1; eng.close()
-    # the first bad record in file order decides the error, whichever chunk meets one first
-    for where, field, what in ((90_001, "l_qseq", "CIGAR and sequence length disagree"), (40_000, "pos", "not coordinate-sorted"), (150_000, "lib", "library index out of range")):
+    # the first bad record in file order decides the error, whichever chunk meets one first: every refusal of the per-read rule, each at
+    # a read behind index 8192 (the pool's threshold), with a later bad record that must not win — on one thread and on the pool
+    n_all = len(arrs["pos"])
+    plain = np.flatnonzero((arrs["n_cigar"] == 1) & ((arrs["flag"] & 0x704) == 0) & (arrs["lib"] >= 0) & (np.arange(n_all) > 8192))     # mapped, counted reads of one M operator
+    cases = ((90_001, "l_qseq", "CIGAR and sequence length disagree"), (40_000, "pos", "not coordinate-sorted"), (150_000, "lib", "library index out of range"),
+             (20_000, "arena", "outside the batch arenas"), (int(plain[5]), "noseq", "without sequence would be counted"),
+             (int(plain[9]), "end", "ends beyond the last 32-bit position"),
+             # (by l_qseq only: read 10 000's rows start 1 - 2 MB into arenas of 10 and 20 MB, so the arena check in front of this one passes)
+             (10_000, "4m", "reads of 4 Mbases and more are not supported"), (int(plain[7]), "empty_m", "empty M/=/X CIGAR operator behind its last base"))
+    for where, field, what in cases:
+        assert 8192 < where and (where < 120_000 or field == "lib")
         bad = {k: (v.copy() if v is not None else None) for k, v in arrs.items()}
         bad["l_qseq"][120_000] += 1                                             # a later bad record that must not win
         if field == "l_qseq": bad["l_qseq"][where] += 2
         elif field == "pos": bad["pos"][where] = bad["pos"][where - 1] - 5
-        else: bad["lib"][where] = 9; bad["l_qseq"][120_000] -= 1
+        elif field == "lib": bad["lib"][where] = 9; bad["l_qseq"][120_000] -= 1
+        elif field == "arena": bad["qual_off"][where] = np.uint64(len(bad["qual"]))
+        elif field == "noseq": bad["l_qseq"][where] = 0
+        elif field == "end": bad["pos"][where] = 2**31 - 10                    # (the read behind it is unsorted now: later in file order)
+        elif field == "4m":
+            bad["l_qseq"][where] = 1 << 22
+            assert int(bad["qual_off"][where]) + (1 << 22) <= len(bad["qual"]) and int(bad["seq_off"][where]) + (1 << 21) <= len(bad["seq4"])
+        else:                                                                   # ... 1D 0M 1D behind the read's only match
+            c0 = int(bad["cigar_off"][where])
+            bad["cigar"] = np.concatenate([bad["cigar"][:c0 + 1], np.array([(1 << 4) | 2, 0, (1 << 4) | 2], np.uint32), bad["cigar"][c0 + 1:]]); bad["n_cigar"][where] = 4
+            bad["cigar_off"] = np.where(np.arange(n_all) > where, bad["cigar_off"] + 3, bad["cigar_off"]).astype(np.uint64)
+        said = []
         for threads in (1, 0):
             eng = capi.Engine(sim_lib, per_lib=True, insertion_centric=True, lib_names=names)
             if threads: sim_lib.lib.brc_set_option(eng.h, 8, threads)
@@ -153,7 +173,46 @@ def test_large_batches_are_staged_on_several_threads_like_on_one(sim_lib, oracle
             with pytest.raises(capi.BrcError) as ei:
                 eng.push_reads(bad)
             assert what in str(ei.value), (where, threads, str(ei.value))
+            said.append(str(ei.value)); eng.close()
+        assert said[0] == said[1], (field, said)
+
+
+def test_max_count_drops_in_a_large_batch_like_in_small_ones(sim_lib):
+    """bam_plp_push's max-count rule (-d) has serial state, so a batch that can reach the count goes through the one-thread pass
+    whatever its size: a batch of 160 000 reads in which the rule drops reads must stage — FHOSTDROP flags, pieces, extent, and
+    with them planes and text — exactly what the same reads stage in batches of 1000."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import synthgen
+    ref, arrs = synthgen.generate(120_000, "tumor200x", seed=21, n_chunks=4)
+    n_all = len(arrs["pos"])
+    assert n_all >= 100_000
+
+    def run(max_cnt, step):
+        eng = capi.Engine(sim_lib, max_cnt=max_cnt)
+        try:
+            eng.begin_region(0, 0, 120_000, ref)
+            for i in range(0, n_all, step):
+                eng.push_reads(arrs if step >= n_all else capi.select_reads(arrs, np.arange(i, min(n_all, i + step))))
+            r = eng.end_region(); return r, eng.format_region("chrS")
+        finally:
             eng.close()
+    r_all, t_all = run(60, n_all); r_small, t_small = run(60, 1000)
+    parity.assert_results_equal(r_all, r_small, "max count: one large batch vs batches of 1000"); assert t_all == t_small
+    r_free, _ = run(0, n_all)
+    assert r_all.n_events < r_free.n_events * 0.9                              # the rule did drop reads
+
+
+def test_host_side_under_the_host_sanitizers():
+    """tests/sim/host_check.cpp: the engine's host code and the simulator built with -fsanitize=address,undefined, driven by a program
+    of its own through the life of an engine — a pooled push, a window behind a fetched result, both ways to the text, a refused push
+    and the next region, the device-text route, max-count drops, destroy.  It checks its own results; a report or a leak fails it."""
+    sim_dir = os.path.join(ROOT, "tests", "sim")
+    subprocess.check_call(["make", "-s", "-C", sim_dir, "asan"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([os.path.join(sim_dir, "host_check_asan")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    assert p.stdout.decode().startswith("host_check ok"), p.stdout.decode()
 
 
 def test_push_reads_refuses_inconsistent_records(sim_lib):
