@@ -16,6 +16,22 @@
 
 namespace brc {
 
+// The coverage witness (brc_sim_witness below): what the pieces of a computed region did inside pileup_tile, as k_pileup2 would count it —
+// which no test can see from outside.  One record per compute() while collecting, as JSON.
+static bool g_wit_on = false;
+static std::string g_wit_json, g_wit_out;
+struct Witness {
+    std::map<std::string, std::vector<uint64_t>> pieces;      // kind -> [ring half][step J] of the pieces that touch their tile
+    std::map<uint32_t, uint64_t> tile_pieces;                 // pieces of a non-empty tile -> tiles
+    uint32_t queue_max = 0, flush_max = 0, pieces_max = 0, ncol_max = 0, halves_max = 0;
+    uint64_t flush_in_drain = 0, flush_regular = 0, lo_parity[2] = {0, 0}, tiles = 0;
+    bool stage_fault = false, windows = false;
+    void count(const std::string& kind, uint32_t step) {
+        std::vector<uint64_t>& v = pieces[kind]; if (v.empty()) v.assign((size_t)2 * HALF, 0);
+        v[(size_t)((step / HALF) % 2u) * HALF + step % HALF]++;
+    }
+};
+
 static void* sim_alloc(size_t n) { return malloc(n ? n : 1); }
 static void sim_release(void* p) { free(p); }
 static const HostAlloc kAlloc = {sim_alloc, sim_release};
@@ -60,6 +76,7 @@ class SimBackend : public Backend {
     }
 
     bool stage_fault = false;            // a staged window outside the padded event-byte stream: the device would fault (checked at the end of compute)
+    Witness wit;
     bool stats_on = false; uint64_t stat_steps = 0, stat_dead = 0;      // BRC_SIM_PIECE_STATS: piece-steps, and those whose piece does not touch the tile
     uint32_t tile_want = 0u | (63u << 8);     // brc_region_windows: the lanes of the current tile that a window asks for
     // one (tile, library) wave of KB
@@ -77,12 +94,20 @@ class SimBackend : public Backend {
         struct QEnt { uint32_t piece; int kind; bool lane[TILE]; };    // kind 0: third-allele events, 1: integers of a huge piece
         std::vector<QEnt> queue;
         int since_flush = 0; bool flushed = false;
+        uint32_t n_flush = 0;
+        if (g_wit_on && lo < hi) {
+            wit.tiles++; wit.lo_parity[lo & 1u]++; wit.tile_pieces[hi - lo]++;
+            if (hi - lo > wit.pieces_max) wit.pieces_max = hi - lo;
+            if ((hi - lo + HALF - 1) / HALF > wit.halves_max) wit.halves_max = (hi - lo + HALF - 1) / HALF;
+        }
         for (uint32_t base = lo; base < hi; base += HALF) {
             const uint32_t nb = hi - base < (uint32_t)HALF ? hi - base : (uint32_t)HALF;
+            uint32_t dev_entries = 0;      // queue entries of this half-batch as k_pileup2 pushes them: N / '=' lanes, huge-integer lanes, third-allele lanes — one each per piece
             for (uint32_t m = base; m < base + nb; ++m) {
                 const Piece& h = hot[m];
                 const uint32_t fl = piece_flags(h);
                 QEnt full, ints; full.piece = ints.piece = m; full.kind = 0; ints.kind = 1; bool any_full = false, any_int = false;
+                bool any_exo = false, any_ovf = false, touches = false;      // (the witness: the two entries the simulator merges into `full`, counted apart)
                 {   // the window of this piece's event bytes the device would stage for this tile must lie inside the padded stream
                     const int32_t p0w = (int32_t)(c.pos0 + tl * TILE);
                     const int64_t w0 = (int64_t)h.bq_off + stage_window_start(p0w, h.a, c.max_lqseq);
@@ -93,7 +118,7 @@ class SimBackend : public Backend {
                     full.lane[l] = ints.lane[l] = false;
                     if (!valid[l]) continue;
                     const uint32_t d = (uint32_t)(p[l] - h.rs);
-                    if (d < (uint32_t)h.ext) a[l].ncol++;                                             // lib_counts[library] (:286)
+                    if (d < (uint32_t)h.ext) { a[l].ncol++; touches = true; }                         // lib_counts[library] (:286)
                     if (!(d < (uint32_t)h.len)) continue;
                     const int qpos = p[l] - h.a;
                     uint32_t w = eb[h.bq_off + (uint64_t)qpos];
@@ -104,7 +129,7 @@ class SimBackend : public Backend {
                     // whatever the slots hold
                     if ((fl & PF_WIDE) && eb_is_escape(w)) {
                         const uint32_t w16 = in.bqw[wide_base(in.bqw, h.bq_off) + (uint64_t)qpos];
-                        if (!bucket_acgt(w16 & 0xffu)) { a[l].ww += h.ww; full.lane[l] = true; any_full = true; continue; }
+                        if (!bucket_acgt(w16 & 0xffu)) { a[l].ww += h.ww; full.lane[l] = true; any_full = any_exo = true; continue; }
                         w = ((w16 >> 8) << 2) | ((w16 & 0xffu) - 1u);
                     }
                     EvTerms t = (fl & (PF_TABLE | PF_TABQ)) ? piece_terms_tab(h, tt, c.table_len, qpos) : (fl & PF_DIV) ? piece_terms_inlane(fl, h.tp_flags, h.w3 >> c.pack_shift, qpos) : piece_terms_div(fl, piece_tp(c, h), rare[m], qpos);
@@ -113,19 +138,30 @@ class SimBackend : public Backend {
                     a[l].ww += h.ww;
                     if (b == a[l].dom_b) { pack_event(a[l].dom, h, t, w); if (fl & PF_HUGE) { ints.lane[l] = true; any_int = true; } }
                     else if (a[l].alt_b == NB_NONE || a[l].alt_b == b) { a[l].alt_b = b; pack_event(a[l].alt, h, t, w); if (fl & PF_HUGE) { ints.lane[l] = true; any_int = true; } }
-                    else { full.lane[l] = true; any_full = true; }
+                    else { full.lane[l] = true; any_full = any_ovf = true; }
+                }
+                if (g_wit_on) {
+                    dev_entries += (any_exo ? 1u : 0u) + (any_int ? 1u : 0u) + (any_ovf ? 1u : 0u);
+                    if (touches) {
+                        std::string kind = h.len == 0 ? "eventless" : (fl & PF_NB) ? "nb" : (fl & PF_TABLE) ? "table" : (fl & PF_TABQ) ? "tabq" : (fl & PF_DIV) ? "div" : "rare";
+                        if (h.len != 0 && (fl & PF_WIDE)) kind += "+wide";
+                        if (h.len != 0 && (fl & PF_HUGE)) kind += "+huge";
+                        wit.count(kind, m - lo);
+                        if (h.ext > h.len) wit.count("ext", m - lo);
+                    }
                 }
                 if (any_full) queue.push_back(full);
                 if (any_int) queue.push_back(ints);
             }
             since_flush += (int)nb;
+            if (g_wit_on && dev_entries > wit.queue_max) wit.queue_max = dev_entries;
             // between half-batches: drain the queue (the event bytes of this half-batch are still staged), flush when the
             // packed fields could overflow during the next half-batch
             for (const QEnt& e : queue) {
                 const Piece& h = hot[e.piece]; const PieceRare rr = rare_of(e.piece);
                 if (e.kind == 1 && !flushed) {                                                        // huge integers go straight to the slot planes: make them live
                     for (int l = 0; l < TILE; ++l) if (valid[l]) lane2_flush(c, pl, lib, kk[l], a[l], false);
-                    flushed = true; since_flush = 0;
+                    flushed = true; since_flush = 0; ++n_flush; wit.flush_in_drain++;
                 }
                 for (int l = 0; l < TILE; ++l) {
                     if (!e.lane[l]) continue;
@@ -140,9 +176,11 @@ class SimBackend : public Backend {
             queue.clear();
             if (since_flush + HALF > c.flush_k) {
                 for (int l = 0; l < TILE; ++l) if (valid[l]) lane2_flush(c, pl, lib, kk[l], a[l], flushed);
-                flushed = true; since_flush = 0;
+                flushed = true; since_flush = 0; ++n_flush; wit.flush_regular++;
             }
         }
+        if (n_flush > wit.flush_max) wit.flush_max = n_flush;
+        for (int l = 0; l < TILE; ++l) if (valid[l] && a[l].ncol > wit.ncol_max) wit.ncol_max = a[l].ncol;
         for (int l = 0; l < TILE; ++l) {
             if (!inreg[l]) continue;
             const bool dead = !valid[l];
@@ -150,6 +188,26 @@ class SimBackend : public Backend {
             if (!dead) { warn[BRC_W_SM_MISSING] += a[l].ww & 0xffffu; warn[BRC_W_NM_MISSING] += a[l].ww >> 16; if (p[l] >= c.beg0) n_events += a[l].ncol; }
             if (dead && lib == 0) warn[BRC_W_LIB_UNAVAILABLE]++;
         }
+    }
+
+    void emit_witness() const {
+        std::string j = "{\"half\": " + std::to_string((int)HALF) + ", \"table_len\": " + std::to_string(c.table_len) + ", \"flush_k\": " + std::to_string(c.flush_k) +
+                        ", \"pack_lim\": " + std::to_string(c.pack_lim) + ", \"pack_shift\": " + std::to_string(c.pack_shift) + ", \"n_pieces\": " + std::to_string(c.n_pieces) +
+                        ", \"tiles\": " + std::to_string(wit.tiles) + ", \"queue_max\": " + std::to_string(wit.queue_max) + ", \"flush_max\": " + std::to_string(wit.flush_max) +
+                        ", \"flush_in_drain\": " + std::to_string(wit.flush_in_drain) + ", \"flush_regular\": " + std::to_string(wit.flush_regular) +
+                        ", \"pieces_max\": " + std::to_string(wit.pieces_max) + ", \"halves_max\": " + std::to_string(wit.halves_max) + ", \"ncol_max\": " + std::to_string(wit.ncol_max) +
+                        ", \"lo_parity\": [" + std::to_string(wit.lo_parity[0]) + ", " + std::to_string(wit.lo_parity[1]) + "], \"stage_fault\": " + (wit.stage_fault ? "true" : "false") +
+                        ", \"windows\": " + (wit.windows ? "true" : "false") + ", \"tile_pieces\": {";
+        bool first = true;
+        for (const auto& kv : wit.tile_pieces) { j += (first ? "\"" : ", \"") + std::to_string(kv.first) + "\": " + std::to_string(kv.second); first = false; }
+        j += "}, \"pieces\": {"; first = true;
+        for (const auto& kv : wit.pieces) {
+            j += (first ? "\"" : ", \"") + kv.first + "\": ["; first = false;
+            for (size_t i = 0; i < kv.second.size(); ++i) j += (i ? ", " : "") + std::to_string(kv.second[i]);
+            j += "]";
+        }
+        j += "}}";
+        g_wit_json += (g_wit_json.empty() ? "" : ", ") + j;
     }
 
     int compute(brc_timing* t) override {
@@ -198,7 +256,7 @@ class SimBackend : public Backend {
         const char* xc = getenv("BRC_XEV_CAP");                                                            // (test knob: a tiny list exercises the grow-and-recompute path)
         if (xev.empty()) xev.resize(xc ? (size_t)atoi(xc) : 1024);
       again:
-        xev_n = 0;
+        xev_n = 0; wit = Witness();
         Planes pl = {ncol.data(), depth.data(), slotid.data(), si.data(), sf.data(), unavail.data(), xev.data(), &xev_n, (uint32_t)xev.size(), 1u};
         n_events = n_positions = 0; memset(warn, 0, sizeof warn);
         const int64_t ntiles = (P + TILE - 1) / TILE;
@@ -290,6 +348,7 @@ class SimBackend : public Backend {
             ib_slots = tmp; ib_cnt = cnt; ib_end.assign((size_t)nbk + 1, 0); for (int64_t b = 0; b < nbk; ++b) ib_end[(size_t)b] = off[(size_t)b] + cnt[(size_t)b];
             have_indel_tables = true;
         }
+        if (g_wit_on) { wit.stage_fault = stage_fault; wit.windows = !wanted.empty(); emit_witness(); }
         if (stage_fault) { stage_fault = false; err = "a tile would stage a window of event bytes outside the padded stream (k_pileup2: BRC_STAGE)"; return BRC_E_HIP; }
         if (stats_on) fprintf(stderr, "piece-steps %llu, of them %llu (%.2f %%) of a piece that does not touch the tile; %.1f events per step\n", (unsigned long long)stat_steps,
                               (unsigned long long)stat_dead, 100.0 * (double)stat_dead / (double)(stat_steps ? stat_steps : 1), (double)n_events / (double)(stat_steps ? stat_steps : 1));
@@ -361,3 +420,16 @@ const char* backend_kind() { return "sim-cpu"; }
 const char* backend_kernel_name(int) { return nullptr; }
 
 }  // namespace brc
+
+// The coverage witness, for tests/test_pileup_boundaries.py (this library only; not part of the C-ABI): reset != 0 — forget what was collected
+// and collect from now on, one record per computed region; reset == 0 — the records collected so far as a JSON list.  Per record: the host's
+// choices (table_len, flush_k, pack_lim, pack_shift: Staged::modal_len and choose_pack, the functions the HIP backend calls too), and of the
+// walk over the tiles' piece ranges: "pieces" — kind -> 2 x HALF counters [ring half][step] of the pieces that touch their tile (kinds: table,
+// tabq, div, rare, nb, each with +wide / +huge where the flags say so, eventless, and ext for every piece with ext > len); "queue_max" — the
+// most deferred entries of one half-batch as k_pileup2 pushes them; flushes; the most pieces, half-batches and columns of a tile; the
+// parity of the tiles' first piece; whether a staged window would have left the padded stream.
+extern "C" __attribute__((visibility("default"))) const char* brc_sim_witness(int reset) {
+    if (reset) { brc::g_wit_on = true; brc::g_wit_json.clear(); return ""; }
+    brc::g_wit_out = "[" + brc::g_wit_json + "]";
+    return brc::g_wit_out.c_str();
+}
