@@ -17,91 +17,22 @@ Third-allele events are held to at most XEV_CAP per (tile, library) bucket in ev
 (ADVICE.md), and this file stays clear of it."""
 import ctypes
 import json
-import os
 
 import numpy as np
 import pytest
 
 import parity
-import synth
 from bam_readcount_amd import capi
-from conftest import ROOT
+from constructed import OTHER, THIRD, Reads, ACGT_CODE, chain, checked_lib, mismatches, ref_of  # noqa: F401  (checked_lib: fixture)
 
 HALF = 12                        # brc_core.h: BRC_HALF (the witness repeats it; asserted)
 QCAP = 3 * HALF + 2              # brc_engine.hip
 XEV_CAP = 512
-CHECKED = os.path.join(ROOT, "bam_readcount_amd", "csrc", "libbrc_hip_checked.so")
-
-_LUT = np.zeros(256, np.uint8); _LUT[[65, 67, 71, 84]] = [1, 2, 4, 8]
-OTHER = np.ones(16, np.uint8); OTHER[[1, 2, 4, 8]] = [2, 4, 8, 1]          # a base that is not the reference's ...
-THIRD = np.full(16, 2, np.uint8); THIRD[[1, 2, 4, 8]] = [4, 8, 1, 2]       # ... and one that is neither
-
-
-class Reads:
-    """Reads written down one by one: add(pos, [(op, len)], ...) takes the bases from the reference, `edit(seq, qual, aq, ar)` then changes
-    them in place (aq / ar: query offset and reference position of every aligned base).  arrays(): the batch, sorted by position (stable),
-    arenas in read order."""
-
-    def __init__(self, ref):
-        self.code = _LUT[ref]; assert self.code.all()
-        self.rows = []
-
-    def add(self, pos, ops, flag=0, mapq=60, lib=0, nm=1, sm=30, tags=3, edit=None):
-        L = sum(l for o, l in ops if o in (0, 1, 4))
-        seq = np.ones(L, np.uint8); qual = (20 + (np.arange(L) * 7 + pos) % 21).astype(np.uint8)
-        aq, ar = [], []; q = 0; r = pos
-        for o, l in ops:
-            if o == 0:
-                aq.append(np.arange(q, q + l)); ar.append(np.arange(r, r + l)); q += l; r += l
-            elif o in (1, 4):
-                q += l
-            else:
-                r += l
-        aq = np.concatenate(aq); ar = np.concatenate(ar)
-        seq[aq] = self.code[ar]
-        if edit:
-            edit(seq, qual, aq, ar, self.code)
-        self.rows.append((pos, ops, flag, mapq, lib, nm, sm, tags, seq, qual))
-
-    def arrays(self):
-        rows = [self.rows[i] for i in np.argsort([r[0] for r in self.rows], kind="stable")]
-        cols = list(zip(*rows))
-        L = np.array([len(s) for s in cols[8]], np.int64); nc = np.array([len(o) for o in cols[1]], np.int64)
-        seq4 = []
-        for s in cols[8]:
-            s = np.append(s, 0) if len(s) & 1 else s
-            seq4.append(((s[0::2] << 4) | s[1::2]).astype(np.uint8))
-        a = dict(pos=cols[0], flag=cols[2], mapq=cols[3], lib=cols[4], l_qseq=L, n_cigar=nc, cigar_off=np.cumsum(nc) - nc,
-                 seq_off=np.cumsum((L + 1) // 2) - (L + 1) // 2, qual_off=np.cumsum(L) - L, nm=cols[5], sm=cols[6], tags=cols[7],
-                 cigar=[(l << 4) | o for ops in cols[1] for o, l in ops], seq4=np.concatenate(seq4), qual=np.concatenate(cols[9]))
-        return {k: np.asarray(v).astype(dt) for k, dt in capi.BATCH_DTYPES.items() for v in [a[k]]}
-
-
-def mismatches(offsets, lut=OTHER, q=None):
-    def edit(seq, qual, aq, ar, code):
-        o = np.asarray([x for x in offsets if x < len(aq)], np.int64)
-        seq[aq[o]] = lut[code[ar[o]]]
-        if q is not None:
-            qual[aq[o]] = q
-    return edit
-
-
-def chain(*edits):
-    def edit(*a):
-        for e in edits:
-            if e:
-                e(*a)
-    return edit
-
 
 class Case:
     def __init__(self, ref, arrs, regions, witness, opts=None, env=None, names=(), windows=None, check_warn=True):
         self.ref, self.arrs, self.regions, self.witness = ref, arrs, regions, witness
         self.opts, self.env, self.names, self.windows, self.check_warn = opts or {}, env or {}, names, windows, check_warn
-
-
-def ref_of(n):
-    return synth.make_ref(np.random.default_rng(20), n)
 
 
 def fillers(R, pos, n):
@@ -292,7 +223,7 @@ def case_d(two_libs):
     """70 000 reads of 100 bases with starts spread over one tile, every seventh carrying a second allele throughout; every 150th a third
     allele at its eleventh base (counted: at most XEV_CAP per bucket).  Built vectorised."""
     n, L, T = 70_000, 100, 1024
-    ref = ref_of(2048); code = _LUT[ref]
+    ref = ref_of(2048); code = ACGT_CODE[ref]
     starts = np.sort(np.random.default_rng(1).integers(T, T + 64, n)).astype(np.int32)
     seq = code[starts[:, None] + np.arange(L)[None, :]]
     seq[::7] = OTHER[seq[::7]]
@@ -415,14 +346,6 @@ def check(lib, oracle_lib, case):
     assert got_text == case.want[0] and got_text.count(b"\n") > 30
     for g, w in zip(got_planes, case.want[1]):
         np.testing.assert_array_equal(g, w)
-
-
-@pytest.fixture(scope="module")
-def checked_lib():
-    """libbrc_hip_checked.so as build() left it (it is not built here: a missing library is an error)"""
-    if not os.path.exists(CHECKED):
-        raise RuntimeError("libbrc_hip_checked.so is not built (make -C bam_readcount_amd/csrc checked)")
-    return capi.Library(CHECKED)
 
 
 # (the checked route stands first: in file order, and in the GPU job, the product runs a batch only after the bounds-checked build did)
