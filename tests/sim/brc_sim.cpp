@@ -26,6 +26,8 @@ struct Witness {
     uint32_t queue_max = 0, flush_max = 0, pieces_max = 0, ncol_max = 0, halves_max = 0;
     uint64_t flush_in_drain = 0, flush_regular = 0, lo_parity[2] = {0, 0}, tiles = 0;
     bool stage_fault = false, windows = false;
+    // the tile ranges and what a compaction of them keeps (tests/test_tile_ranges.py): see brc_sim_witness
+    uint64_t ranged = 0, live = 0, live_clipped = 0, range_max = 0, live_max = 0, live_max_read = 0, reads_max = 0, starts_behind = 0;
     void count(const std::string& kind, uint32_t step) {
         std::vector<uint64_t>& v = pieces[kind]; if (v.empty()) v.assign((size_t)2 * HALF, 0);
         v[(size_t)((step / HALF) % 2u) * HALF + step % HALF]++;
@@ -41,7 +43,7 @@ class SimBackend : public Backend {
     const Staged* st = nullptr;
     std::vector<DRead> reads; std::vector<uint8_t> eb; std::vector<uint32_t> wbuf; size_t bq_n = 0;      // wbuf: the sparse wide stream, table then rows (DevIn.bqw)
      std::vector<float> tq; std::vector<double> te;
-    std::vector<Piece> hot; std::vector<PieceRare> rare; std::vector<int32_t> key, reach, prefmax;
+    std::vector<Piece> hot; std::vector<PieceRare> rare; std::vector<int32_t> key, reach, prefmax; std::vector<uint32_t> piece_read;
     // the rare record of piece m: stored by K1 only when piece_has_rare(flags), derived from the piece otherwise
     PieceRare rare_of(uint32_t m) const { return piece_has_rare(piece_flags(hot[m])) ? rare[m] : piece_rare_of(c, hot[m]); }
     std::vector<uint32_t> ncol, depth, slotid, si, unavail; std::vector<float> sf; std::vector<XEv> xev; uint32_t xev_n = 0;
@@ -197,7 +199,12 @@ class SimBackend : public Backend {
                         ", \"flush_in_drain\": " + std::to_string(wit.flush_in_drain) + ", \"flush_regular\": " + std::to_string(wit.flush_regular) +
                         ", \"pieces_max\": " + std::to_string(wit.pieces_max) + ", \"halves_max\": " + std::to_string(wit.halves_max) + ", \"ncol_max\": " + std::to_string(wit.ncol_max) +
                         ", \"lo_parity\": [" + std::to_string(wit.lo_parity[0]) + ", " + std::to_string(wit.lo_parity[1]) + "], \"stage_fault\": " + (wit.stage_fault ? "true" : "false") +
-                        ", \"windows\": " + (wit.windows ? "true" : "false") + ", \"tile_pieces\": {";
+                        ", \"windows\": " + (wit.windows ? "true" : "false") +
+                        ", \"ranged\": " + std::to_string(wit.ranged) + ", \"live\": " + std::to_string(wit.live) + ", \"live_clipped\": " + std::to_string(wit.live_clipped) +
+                        ", \"range_max\": " + std::to_string(wit.range_max) + ", \"live_max\": " + std::to_string(wit.live_max) + ", \"live_max_read\": " + std::to_string(wit.live_max_read) +
+                        ", \"reads_max\": " + std::to_string(wit.reads_max) + ", \"range_starts_behind_next\": " + std::to_string(wit.starts_behind) +
+                        ", \"n_reads\": " + std::to_string(c.n_reads) + ", \"ntiles\": " + std::to_string((c.P + TILE - 1) / TILE) + ", \"Lp\": " + std::to_string(c.Lp) +
+                        ", \"pos0\": " + std::to_string(c.pos0) + ", \"P\": " + std::to_string(c.P) + ", \"tile_pieces\": {";
         bool first = true;
         for (const auto& kv : wit.tile_pieces) { j += (first ? "\"" : ", \"") + std::to_string(kv.first) + "\": " + std::to_string(kv.second); first = false; }
         j += "}, \"pieces\": {"; first = true;
@@ -225,7 +232,7 @@ class SimBackend : public Backend {
         }
         uint16_t* const bqw_w = const_cast<uint16_t*>(in.bqw);
         hot.assign((size_t)np + 1, Piece()); { PieceRare poison; memset(&poison, 0xff, sizeof poison); rare.assign((size_t)np + 1, poison); }   // (a rare record nobody wrote must not be read)
-        key.assign((size_t)np + 1, 0); reach.assign((size_t)np + 1, 0); prefmax.assign((size_t)np + 1, 0);
+        key.assign((size_t)np + 1, 0); reach.assign((size_t)np + 1, 0); prefmax.assign((size_t)np + 1, 0); piece_read.assign((size_t)np + 1, 0);
         unavail.assign((size_t)PS, NONE32);
         for (int64_t i = 0; i < n; ++i) {                                                             // K1
             bool wide = false;
@@ -241,7 +248,7 @@ class SimBackend : public Backend {
             walk_pieces(c.insertion_centric != 0, enters && !nolib, rc.counts, rd.pos, cg, in.n_cigar[i], [&](int32_t rs, int32_t len, int32_t ext, int qoff, bool nb) {
                 PieceRare rr; make_piece(c, rc, rs, len, ext, qoff, nb, hot[slot], rr, c.pack_shift);
                 if (piece_has_rare(piece_flags(hot[slot]))) rare[slot] = rr;
-                key[slot] = rd.pos; reach[slot] = rs + ext; ++slot; ++cnt;
+                key[slot] = rd.pos; reach[slot] = rs + ext; piece_read[slot] = (uint32_t)i; ++slot; ++cnt;
             });
             if (cnt != st->piece_cnt.p[i]) { err = "piece count of the host and of K1 differ"; return BRC_E_ARG; }
         }
@@ -265,16 +272,11 @@ class SimBackend : public Backend {
             const int64_t s0 = st->lib_base[(size_t)l], s1 = st->lib_base[(size_t)l + 1];
             int32_t m = INT32_MIN;
             for (int64_t i = s0; i < s1; ++i) { if (reach[(size_t)i] > m) m = reach[(size_t)i]; prefmax[(size_t)i] = m; }
+            uint32_t lo_before = 0, gx = 0xffffffffu, gy = 0;                                          // (the witness: the tile before, the group of 8 tiles)
             for (int64_t tl = 0; tl < ntiles; ++tl) {                                                 // KB
                 uint32_t lo, hi; tile_range2(c, prefmax.data(), key.data(), s0, s1, tl, lo, hi);
-                if (!wanted.empty() && wanted[(size_t)tl] == (uint16_t)TILE_UNWANTED) {
-                    // brc_region_windows: exactly what k_mask_tiles leaves of a tile nobody announced — no column, no depth, no slot;
-                    // its statistics planes are never written (and must never be read: they keep their poison here)
-                    for (int ln = 0; ln < TILE; ++ln) { const int64_t k = tl * TILE + ln; if (k >= P) break;
-                        ncol[(size_t)(l * PS + k)] = 0; depth[(size_t)(l * PS + k)] = 0; slotid[(size_t)(l * PS + k)] = (uint32_t)NB_NONE | ((uint32_t)NB_NONE << 8); }
-                    continue;
-                }
-                if (!wanted.empty()) {
+                const bool unwanted = !wanted.empty() && wanted[(size_t)tl] == (uint16_t)TILE_UNWANTED;
+                if (!wanted.empty() && !unwanted) {
                     // an announced tile is piled up for the lanes its windows ask for: pieces that cannot reach them are trimmed off
                     // both ends of its range (k_mask_tiles), the other lanes behave like lanes outside the region
                     const uint32_t w = wanted[(size_t)tl];
@@ -283,6 +285,36 @@ class SimBackend : public Backend {
                     while (hi > lo && (int64_t)key[hi - 1] > p1w) --hi;
                     tile_want = w;
                 } else tile_want = 0u | (63u << 8);
+                if (g_wit_on) {      // the range as the compaction kernels find it in rng[] (every tile, announced or not), and what they keep of it
+                    const int64_t p0 = (int64_t)c.pos0 + tl * TILE, p1 = p0 + TILE, p1c = p1 < (int64_t)c.pos0 + P ? p1 : (int64_t)c.pos0 + P;
+                    uint64_t lv = 0, lvc = 0, of_read = 0;
+                    for (uint32_t m = lo; m < hi; ++m) {
+                        const int64_t rs = hot[m].rs, re = rs + hot[m].ext;
+                        if (m > lo && piece_read[m] != piece_read[m - 1]) of_read = 0;
+                        if (rs < p1 && re > p0) { ++lv; if (++of_read > wit.live_max_read) wit.live_max_read = of_read; }
+                        if (rs < p1c && re > p0) ++lvc;
+                    }
+                    wit.ranged += hi - lo; wit.live += lv; wit.live_clipped += lvc;
+                    if (hi - lo > wit.range_max) wit.range_max = hi - lo;
+                    if (lv > wit.live_max) wit.live_max = lv;
+                    if (tl > 0 && lo_before > lo) wit.starts_behind++;
+                    lo_before = lo;
+                    if (tl % 8 == 0) { gx = 0xffffffffu; gy = 0; }
+                    if (lo < hi) { if (lo < gx) gx = lo; if (hi > gy) gy = hi; }
+                    if ((tl % 8 == 7 || tl == ntiles - 1) && gx < gy) {      // the reads a wave of k_compact_reads visits for this group of 8 tiles
+                        uint64_t nr = 0;
+                        if (Lp == 1) { for (int64_t rd = piece_read[gx]; rd < n && st->piece_off.p[rd] < gy; ++rd) ++nr; }
+                        else nr = (uint64_t)piece_read[gy - 1] - piece_read[gx] + 1;
+                        if (nr > wit.reads_max) wit.reads_max = nr;
+                    }
+                }
+                if (unwanted) {
+                    // brc_region_windows: exactly what k_mask_tiles leaves of a tile nobody announced — no column, no depth, no slot;
+                    // its statistics planes are never written (and must never be read: they keep their poison here)
+                    for (int ln = 0; ln < TILE; ++ln) { const int64_t k = tl * TILE + ln; if (k >= P) break;
+                        ncol[(size_t)(l * PS + k)] = 0; depth[(size_t)(l * PS + k)] = 0; slotid[(size_t)(l * PS + k)] = (uint32_t)NB_NONE | ((uint32_t)NB_NONE << 8); }
+                    continue;
+                }
                 pileup_tile(pl, l, tl, lo, hi);
             }
         }
@@ -428,6 +460,13 @@ const char* backend_kernel_name(int) { return nullptr; }
 // tabq, div, rare, nb, each with +wide / +huge where the flags say so, eventless, and ext for every piece with ext > len); "queue_max" — the
 // most deferred entries of one half-batch as k_pileup2 pushes them; flushes; the most pieces, half-batches and columns of a tile; the
 // parity of the tiles' first piece; whether a staged window would have left the padded stream.
+// For tests/test_tile_ranges.py, of the piece range [lo, hi) of EVERY (tile, library) — tile_range2, trimmed as k_narrow_tiles trims an
+// announced tile, whole for a tile nobody announced (the pileup skips it, the compaction kernels total it) —: "ranged" = the sum of hi - lo;
+// "live" = the pieces of the ranges whose [rs, rs + ext) meets [p0, p0 + 64) (what k_compact_tiles keeps), "live_clipped" = the same
+// against [p0, min(p0 + 64, pos0 + P)) (what k_compact_reads keeps); "range_max", "live_max", "live_max_read" (the most live pieces one
+// read has in one tile), "reads_max" (the most reads a wave of k_compact_reads visits for one group of 8 tiles: from the read that holds
+// the group's first slot to the last read whose slots start inside its range), "range_starts_behind_next" (adjacent tiles with
+// lo(t) > lo(t + 1): only trimming does that), and n_reads, ntiles, Lp, pos0, P.
 extern "C" __attribute__((visibility("default"))) const char* brc_sim_witness(int reset) {
     if (reset) { brc::g_wit_on = true; brc::g_wit_json.clear(); return ""; }
     brc::g_wit_out = "[" + brc::g_wit_json + "]";
