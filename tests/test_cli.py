@@ -714,3 +714,43 @@ def test_cli_ranks_equal_single_process_cpu(synthetic_bam):
 def test_cli_ranks_equal_single_process_gpu(synthetic_bam):
     """world 2, 3 and 4 on ONE GPU (BRC_DEVICES=0,0,..): every rank a process of its own with its own HIP context"""
     _ranks_check(HIP_CLI, synthetic_bam, devices=0)
+
+
+def test_cli_pure_parts_under_the_host_sanitizers():
+    """tests/sim/cli_check.cpp: the knob table (every knob against the rule of its group: unset, "", 0, 1, -1, abc, a large value), the
+    parsers of --brc-rank-of, -l lines and regions at the boundary forms their comments name, and rank_slice (contiguous, ordered, covering;
+    three vectors worked out by hand with shard.partition's rule), built with -fsanitize=address,undefined as a program of its own."""
+    sim_dir = os.path.join(ROOT, "tests", "sim")
+    subprocess.check_call(["make", "-s", "-C", sim_dir, "cli_check_asan"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
+    p = subprocess.run([os.path.join(sim_dir, "cli_check_asan")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    assert p.stdout.decode().startswith("cli_check ok"), p.stdout.decode()
+
+
+def test_cli_under_the_host_sanitizers_equals_plain_cpu(synthetic_bam):
+    """The command line's own code built with -fsanitize=address,undefined (tests/sim/Makefile: cli-asan; a stand-alone executable over
+    the plain libbrc_sim.so) prints what the plain build prints — stdout, stderr, exit code — and no report: striped BAM and CRAM
+    fetches, a planned site list in small sub-batches, two engines, two ranks, and a run that an invalid region ends.
+    (detect_leaks=0: the program leaves by _exit on purpose.)"""
+    sim_dir = os.path.join(ROOT, "tests", "sim")
+    subprocess.check_call(["make", "-s", "-C", sim_dir, "all", "cli-asan"])
+    d = synthetic_bam
+    rng = np.random.default_rng(13)
+    sl = _sites_file(d, "sites_asan.txt", [("chrA", int(p), int(p)) for p in rng.integers(1, 5000, 60)] + [("chrB", 10, 40), ("chrA", 100, 100), ("nochr", 5, 9)])
+    stripes = dict(BRC_FETCH_STRIPE_MIN="1", BRC_FETCH_THREADS="4")
+    runs = [(["-w", "0", "-p", "-f", "syn.fa", "--brc-chunk", "700", "syn.bam", "chrA:1-3000"], stripes),
+            (["-w", "0", "-f", "syn.fa", "--brc-chunk", "700", "syn.cram", "chrA:1-3000"], stripes),
+            (["-w", "3", "-f", "syn.fa", "-l", sl, "--brc-plan", "16", "syn.bam"], dict(BRC_PLAN_VMAX="700")),
+            (["-w", "0", "--brc-chunk", "333", "--brc-gpus", "2", "-f", "syn.fa", "syn.bam", "chrA"], {}),
+            (["-w", "0", "--brc-chunk", "333", "--brc-ranks", "2", "-f", "syn.fa", "syn.bam", "chrA"], dict(BRC_RANK_CUT="257")),
+            (["-w", "0", "-f", "syn.fa", "syn.bam", "chrA:1-50", "nochr:1-2", "chrB:1-5"], {})]
+    base = dict(os.environ); base.pop("BRC_DEVICES", None); base.pop("BRC_RANKS", None)
+    for args, extra in runs:
+        env = dict(base, ASAN_OPTIONS="detect_leaks=0", UBSAN_OPTIONS="print_stacktrace=1", **extra)
+        want = subprocess.run([SIM_CLI] + args, cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+        got = subprocess.run([SIM_CLI + "-asan"] + args, cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+        assert b"Sanitizer" not in got.stderr and b"runtime error" not in got.stderr, (args, got.stderr[-3000:])
+        assert got.returncode == want.returncode == (1 if "nochr:1-2" in args else 0), (args, got.returncode, want.returncode, got.stderr[-2000:])
+        assert got.stdout == want.stdout and len(want.stdout) > 1000, args
+        assert got.stderr == want.stderr, (args, got.stderr[-2000:], want.stderr[-2000:])
