@@ -20,6 +20,8 @@ namespace brc {
 // which no test can see from outside.  One record per compute() while collecting, as JSON.
 static bool g_wit_on = false;
 static std::string g_wit_json, g_wit_out;
+static bool g_twit_on = false;                                // the text witness (brc_sim_text_witness below): one record per text_begin that wrote its lines
+static std::string g_twit_json, g_twit_out;
 struct Witness {
     std::map<std::string, std::vector<uint64_t>> pieces;      // kind -> [ring half][step J] of the pieces that touch their tile
     std::map<uint32_t, uint64_t> tile_pieces;                 // pieces of a non-empty tile -> tiles
@@ -46,7 +48,7 @@ class SimBackend : public Backend {
     std::vector<Piece> hot; std::vector<PieceRare> rare; std::vector<int32_t> key, reach, prefmax; std::vector<uint32_t> piece_read;
     // the rare record of piece m: stored by K1 only when piece_has_rare(flags), derived from the piece otherwise
     PieceRare rare_of(uint32_t m) const { return piece_has_rare(piece_flags(hot[m])) ? rare[m] : piece_rare_of(c, hot[m]); }
-    std::vector<uint32_t> ncol, depth, slotid, si, unavail; std::vector<float> sf; std::vector<XEv> xev; uint32_t xev_n = 0;
+    std::vector<uint32_t> ncol, depth, slotid, si, unavail; std::vector<float> sf; std::vector<XEv> xev; uint32_t xev_n = 0, xev_bucket_max = 0;
     std::vector<IndelOut> iout;
     // the side tables a text lane reads (brc_core.h: TextAux), in the kernels' layout: folded third-allele records per (tile, library) bucket,
     // reduced indel buckets in their slots
@@ -324,7 +326,7 @@ class SimBackend : public Backend {
             const int64_t nxb = ntiles * Lp;
             std::vector<uint32_t> cnt((size_t)nxb + 1, 0), off((size_t)nxb + 1, 0);
             for (uint32_t i = 0; i < xev_n; ++i) cnt[(size_t)((int64_t)(xev[i].k >> 6) * Lp + (xev[i].lib_b >> 8))]++;
-            uint32_t run = 0; for (int64_t b = 0; b < nxb; ++b) { off[(size_t)b] = run; run += cnt[(size_t)b]; }
+            uint32_t run = 0; xev_bucket_max = 0; for (int64_t b = 0; b < nxb; ++b) { off[(size_t)b] = run; run += cnt[(size_t)b]; if (cnt[(size_t)b] > xev_bucket_max) xev_bucket_max = cnt[(size_t)b]; }
             std::vector<uint32_t> idx(run + 1), cur(off);
             for (int64_t i = (int64_t)xev_n - 1; i >= 0; --i) idx[cur[(size_t)((int64_t)(xev[(size_t)i].k >> 6) * Lp + (xev[(size_t)i].lib_b >> 8))]++] = (uint32_t)i;    // reversed on purpose: the fold must not depend on scatter order
             xagg.assign(run + 1, XAgg()); xagg_end.assign((size_t)nxb + 1, 0); xagg_cnt.assign((size_t)nxb + 1, 0); xagg_list.clear();
@@ -409,7 +411,61 @@ class SimBackend : public Backend {
         if (total64 != (uint64_t)t_off[(size_t)c.P] || total64 > limit) { t_slot ^= 1; return BRC_TEXT_TOO_LONG; }     // (as the HIP backend: 32-bit offsets cannot address it)
         t_text.assign((size_t)t_off[(size_t)c.P] + 1, 0);
         for (int64_t k = 0; k < c.P; ++k) if (t_off[(size_t)k + 1] > t_off[(size_t)k]) (void)text_line(c, in, pl_last, t, ax, k, t_text.data() + t_off[(size_t)k]);
+        if (g_twit_on) emit_text_witness(ax, t_off, t_last[t_slot]);
         return BRC_OK;
+    }
+    // The text witness (brc_sim_text_witness below): where text_line found the sums of every bucket it printed — its own choice between the
+    // two slots and the third-allele table, repeated here over the planes and tables the lines were written from.
+    void emit_text_witness(const TextAux& ax, const std::vector<uint32_t>& t_off, const std::vector<uint32_t>& last) const {
+        static const char* const src_name[5] = {"slot0", "slot1", "table", "table_named", "empty"};
+        std::vector<uint64_t> cell((size_t)5 * NBUCKET * TILE, 0), first((size_t)5 * NBUCKET, 0), lastt((size_t)5 * NBUCKET, 0);
+        uint64_t searched_max = 0, records_max = 0, lines = 0, blocks = 0;
+        const int64_t ntiles = (c.P + TILE - 1) / TILE;
+        for (int64_t k = 0; k < c.P; ++k) {
+            if (t_off[(size_t)k + 1] == t_off[(size_t)k]) continue;
+            ++lines; uint64_t searched = 0;
+            for (int l = 0; l < c.Lp; ++l) {
+                if (ncol[(size_t)(l * c.PS + k)] == 0) continue;
+                ++blocks;
+                const uint32_t sid = slotid[(size_t)(l * c.PS + k)], b0 = sid & 0xffu, b1 = (sid >> 8) & 0xffu;
+                uint32_t x0 = 0u, x1 = 0u;
+                if (ax.xagg) { const int64_t xb = (k >> 6) * c.Lp + l; x1 = ax.xagg_end[xb]; x0 = x1 - ax.xagg_cnt[xb]; }
+                if (x1 - x0 > records_max) records_max = x1 - x0;
+                for (uint32_t b = 0; b < (uint32_t)NBUCKET; ++b) {
+                    const int sl = b == b0 ? 0 : (b == b1 ? 1 : -1);
+                    int src = 4;
+                    if (sl >= 0 && si[(size_t)((((int64_t)l * 2 + sl) * NI + I_N) * c.PS + k)] != 0) src = sl;
+                    else for (uint32_t x = x0; x < x1; ++x) { ++searched; if (ax.xagg[x].k == (uint32_t)k && (ax.xagg[x].lib_b & 0xffu) == b) { src = sl >= 0 ? 3 : 2; break; } }
+                    cell[((size_t)src * NBUCKET + b) * TILE + (size_t)(k & 63)]++;
+                    if ((k >> 6) == 0) first[(size_t)src * NBUCKET + b]++;
+                    if ((k >> 6) == ntiles - 1) lastt[(size_t)src * NBUCKET + b]++;
+                }
+            }
+            if (searched > searched_max) searched_max = searched;
+        }
+        std::string j = "{\"P\": " + std::to_string(c.P) + ", \"Lp\": " + std::to_string(c.Lp) + ", \"pos0\": " + std::to_string(c.pos0) + ", \"ibucket_shift\": " + std::to_string(c.ibucket_shift) +
+                        ", \"lines\": " + std::to_string(lines) + ", \"blocks\": " + std::to_string(blocks) + ", \"total\": " + std::to_string(t_off[(size_t)c.P]) +
+                        ", \"searched_max\": " + std::to_string(searched_max) + ", \"records_max\": " + std::to_string(records_max) + ", \"xev_bucket_max\": " + std::to_string(xev_bucket_max) +
+                        ", \"last_tile_lanes\": " + std::to_string(c.P - (ntiles - 1) * TILE) + ", \"last_processed\": [";
+        for (size_t l = 0; l < last.size(); ++l) j += (l ? ", " : "") + std::to_string(last[l] == NONE32 ? -1ll : (long long)last[l]);
+        j += "]";
+        auto table = [&](const char* name, const std::vector<uint64_t>& v, size_t per) {
+            j += std::string(", \"") + name + "\": {";
+            for (int s = 0; s < 5; ++s) {
+                j += std::string(s ? ", \"" : "\"") + src_name[s] + "\": [";
+                for (size_t b = 0; b < (size_t)NBUCKET; ++b) {
+                    if (per == 1) { j += (b ? ", " : "") + std::to_string(v[(size_t)s * NBUCKET + b]); continue; }
+                    j += b ? ", [" : "[";
+                    for (size_t x = 0; x < per; ++x) j += (x ? ", " : "") + std::to_string(v[((size_t)s * NBUCKET + b) * per + x]);
+                    j += "]";
+                }
+                j += "]";
+            }
+            j += "}";
+        };
+        table("cells", cell, (size_t)TILE); table("first_tile", first, 1); table("last_tile", lastt, 1);
+        j += "}";
+        g_twit_json += (g_twit_json.empty() ? "" : ", ") + j;
     }
     void list_sizes(uint64_t* nx, uint64_t* ni) override { *nx = xev_n; *ni = iout.size(); }
     int text_wait(int slot, HostText* out) override {
@@ -471,4 +527,19 @@ extern "C" __attribute__((visibility("default"))) const char* brc_sim_witness(in
     if (reset) { brc::g_wit_on = true; brc::g_wit_json.clear(); return ""; }
     brc::g_wit_out = "[" + brc::g_wit_json + "]";
     return brc::g_wit_out.c_str();
+}
+
+// The text witness, for tests/test_text_boundaries.py (this library only; not part of the C-ABI): reset > 0 — forget and collect from now on,
+// reset < 0 — forget and stop collecting, reset == 0 — the records so far as a JSON list.  One record per text_begin that wrote its lines (a
+// region handed back to the host's formatter leaves none).  "cells" / "first_tile" / "last_tile": for every bucket of every printed library
+// block where text_line found its sums — "slot0", "slot1", "table" (the folded third-allele records of the (tile, library)), "table_named"
+// (in the table although a slot names the bucket: the events of an N / '=' read base never enter the slots), "empty" — by bucket (= A C G T N)
+// and, for "cells", lane in the tile.  "searched_max": the most table records one line looked at, "records_max": the most records of one
+// (tile, library) table a printed block searched; "lines", "blocks", "total" (bytes, the lead position's line included), "last_processed"
+// per library (-1: never), P, Lp, pos0, ibucket_shift and the lanes of the last tile; "xev_bucket_max": the most third-allele events of one
+// (tile, library) bucket, as the device lists them before the fold.
+extern "C" __attribute__((visibility("default"))) const char* brc_sim_text_witness(int reset) {
+    if (reset) { brc::g_twit_on = reset > 0; brc::g_twit_json.clear(); return ""; }
+    brc::g_twit_out = "[" + brc::g_twit_json + "]";
+    return brc::g_twit_out.c_str();
 }

@@ -1,7 +1,8 @@
 // host_check — the engine's host side (brc_host.cpp) over the CPU lane simulator as a stand-alone program for the host sanitizers
 // (make asan: -fsanitize=address,undefined; tests/test_sim_parity.py runs it).  One walk through the life of an engine: create, a region
 // with a pooled push, a window fetched behind the whole-region result, both ways to the text (brc_format_region and its parts), a
-// refused push and the next region (pushed on one thread, in two batches), the device-text route, the max-count rule, destroy.  Every
+// refused push and the next region (pushed on one thread, in two batches), the device-text route, its line patcher regrowing its buffer
+// in the middle of a line (the sanitizer's realloc always moves: a pointer kept across it is a report), the max-count rule, destroy.  Every
 // step checks what it returns; the texts of the same reads must be the same bytes whichever way they came.
 #include <stdio.h>
 #include <stdlib.h>
@@ -62,6 +63,48 @@ Reads make_reads(const std::string& ref, size_t n) {
         for (int32_t j = 0; j < lq; ++j) r.qual.push_back((uint8_t)(2 + rnd() % 40));
     }
     return r;
+}
+// one read written down by hand: its bases are the reference's under the M operators
+void add_read(Reads& r, const std::string& ref, int32_t pos, const std::vector<std::pair<int, int> >& ops, int16_t lib) {
+    int32_t lq = 0; for (const auto& o : ops) if (o.first == 0 || o.first == 1 || o.first == 4) lq += o.second;
+    r.pos.push_back(pos); r.l_qseq.push_back(lq); r.flag.push_back(0); r.mapq.push_back(50); r.lib.push_back(lib); r.nm.push_back(1); r.sm.push_back(30);
+    r.tags.push_back((uint8_t)(BRC_TAG_NM | BRC_TAG_SM));
+    r.cigar_off.push_back(r.cigar.size()); r.seq_off.push_back(r.seq4.size()); r.qual_off.push_back(r.qual.size()); r.n_cigar.push_back((uint32_t)ops.size());
+    std::vector<uint8_t> codes; int32_t x = pos;
+    for (const auto& o : ops) {
+        r.cigar.push_back(((uint32_t)o.second << 4) | (uint32_t)o.first);
+        if (o.first == 0) for (int j = 0; j < o.second; ++j, ++x) { const char c = ref[(size_t)x]; codes.push_back(c == 'A' ? 1 : c == 'C' ? 2 : c == 'G' ? 4 : 8); }
+        else if (o.first == 2) x += o.second;
+        else for (int j = 0; j < o.second; ++j) codes.push_back(1);
+    }
+    for (size_t j = 0; j < codes.size(); j += 2) r.seq4.push_back((uint8_t)((codes[j] << 4) | (j + 1 < codes.size() ? codes[j + 1] : 0)));
+    for (int32_t j = 0; j < lq; ++j) r.qual.push_back(30);
+}
+// The line patcher of the device-text route (brc_host.cpp: format_device_text) with more to write than its buffer holds: a region that ends at
+// the due position of 400 deletion alleles of 1 .. 400 bases leaves them pending; the next region's reads are plain, so the device's line at
+// that position is some 150 bytes and the rewritten one about 100 KB — in a buffer that starts with 64 KiB and is regrown while the line is
+// being written.  The text of the second region; the same steps through the host's own formatter (device_text == 0) are the expected value.
+int patched_line(const std::string& ref, bool device_text, std::string* out) {
+    brc_config cfg; memset(&cfg, 0, sizeof cfg);
+    cfg.abi_version = BRC_ABI_VERSION;
+    brc_engine* e = nullptr; brc_result res; std::vector<uint64_t> off; const char* t = nullptr; size_t n = 0;
+    OK(brc_create(&cfg, &e));
+    if (device_text) { OK(brc_set_option(e, BRC_OPT_TEXT_ONLY, 1)); OK(brc_set_option(e, BRC_OPT_DEVICE_TEXT, 1)); OK(brc_set_chrom(e, "chrS")); }
+    const int32_t D = 500;
+    Reads pending, plain;
+    for (int d = 1; d <= 400; ++d) add_read(pending, ref, D - 20, {{0, 20}, {2, d}, {0, 10}}, 0);
+    for (int32_t p = 440; p < 520; p += 20) add_read(plain, ref, p, {{0, 80}}, 0);
+    for (int step = 0; step < 2; ++step) {
+        const Reads& use = step ? plain : pending;
+        OK(brc_begin_region(e, 0, step ? D - 5 : D - 10, step ? D + 5 : D, ref.data(), (int64_t)ref.size()));
+        const brc_read_batch b = use.batch(0, use.pos.size(), &off);
+        OK(brc_push_reads(e, &b));
+        OK(brc_end_region(e, &res));
+        OK(brc_format_region(e, &res, "chrS", &t, &n));              // (no brc_clear_indel_queue: the queue lives across the regions)
+    }
+    out->assign(t, n);
+    brc_destroy(e);
+    return 0;
 }
 // one region over the reads (pushed in batches of `step`) up to its result
 int region(brc_engine* e, const std::string& ref, const Reads& r, size_t step, brc_result* res) {
@@ -133,6 +176,15 @@ int main() {
     if (text_of(e, &res, &text_b)) return 1;
     CHECK(text_b == text_a);
     brc_destroy(e); e = nullptr;
+
+    // the line patcher with a line of 100 KB to rewrite: its buffer is regrown in the middle of the line
+    {
+        std::string dev, host;
+        if (patched_line(ref, true, &dev) || patched_line(ref, false, &host)) return 1;
+        size_t entries = 0;
+        for (size_t i = 0; i + 1 < dev.size(); ++i) if (dev[i] == '\t' && dev[i + 1] == '-') ++entries;
+        CHECK(dev == host && dev.size() > 65536 + 16384 && entries == 400);
+    }
 
     // the max-count rule (one-thread pass whatever the batch's size): one large batch drops what batches of 1000 drop
     cfg.max_cnt = 15;

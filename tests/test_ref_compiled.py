@@ -25,6 +25,7 @@ from test_cli import synthetic_bam  # noqa: F401  (fixture)
 from conftest import GOLDEN, ROOT
 import parity
 import synth
+from constructed import queue_expectations, queue_scenarios, run_steps
 
 REF_TREE = "/root/reference"
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
@@ -582,6 +583,22 @@ def test_pending_deletion_blocks_the_queue_like_the_reference_gpu(hip_lib, ref_l
         for route in (dict(), dict(text_only=True), dict(device_text="chrS")):
             got, _ = parity.run_engine(hip_lib, arrs, regions, ref=ref, clear_queue=False, **route, **kw)
             assert got == want, (kw, route)
+
+
+QUEUE_SCENARIOS = queue_scenarios()
+
+
+@pytest.mark.parametrize("name", list(QUEUE_SCENARIOS))
+def test_constructed_queue_scenarios_equal_reference_compiled(oracle_lib, ref_lib, name):
+    """The hand-written regions of tests/test_text_boundaries.py (family E2) that do not start from clean deletion queues — a pending
+    deletion due before, at the first line of, inside, at the last line of and behind the next region, on a bucket edge and on plane index
+    0, from another tid, with one busy library of two — through IndelQueue::process itself: the oracle, which is the expected value of
+    those tests, prints what the reference's own sources print."""
+    ref, steps, kw = QUEUE_SCENARIOS[name]
+    want, _ = run_steps(ref_lib, steps, ref=ref, **kw)
+    got, _ = run_steps(oracle_lib, steps, ref=ref, **kw)
+    assert got == want
+    queue_expectations(name, want)                                   # (what the scenario was built to show, in the reference's own text)
 
 
 def random_scenario(seed, big=False):
