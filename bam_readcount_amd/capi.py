@@ -20,7 +20,7 @@ F_NAMES = ["sev", "sq2", "snm", "s3p"]
 EXPORTS = [
     "brc_strerror", "brc_last_error", "brc_kernel_name", "brc_engine_kind", "brc_create", "brc_destroy",
     "brc_begin_region", "brc_push_reads", "brc_upload", "brc_compute", "brc_fetch_result", "brc_end_region",
-    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows", "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts", "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned", "brc_region_piece_steps", "brc_device_view_get", "brc_device_indels_get",
+    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows", "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts", "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned", "brc_region_piece_steps", "brc_region_passes", "brc_device_view_get", "brc_device_indels_get",
 ]
 
 
@@ -146,6 +146,8 @@ class Library:
             L.brc_host_free.restype = None; L.brc_host_free.argtypes = [C.c_void_p]
         if hasattr(L, "brc_region_piece_steps"):
             L.brc_region_piece_steps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        if hasattr(L, "brc_region_passes"):
+            L.brc_region_passes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.brc_upload.argtypes = [C.c_void_p]
         L.brc_compute.argtypes = [C.c_void_p, C.POINTER(Timing)]
         if hasattr(L, "brc_compute_n"):
@@ -415,6 +417,13 @@ class Engine:
         """(ranged, walked) piece-steps of the last compute (brc_region_piece_steps); (0, 0) when the region was not compacted"""
         a, b = C.c_uint64(), C.c_uint64()
         self._check(self.L.lib.brc_region_piece_steps(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def passes(self):
+        """(passes, xev_cap): how often the last compute ran the pipeline and the entries one third-allele sub-list holds now
+        (brc_region_passes)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self.L.lib.brc_region_passes(self.h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
     def clear_indel_queue(self):

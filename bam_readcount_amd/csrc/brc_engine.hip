@@ -2288,6 +2288,7 @@ class HipBackend : public Backend {
     unsigned long long h_steps[3] = {0, 0, 0};   // piece-steps of the last pass: what the tile ranges hold / what k_pileup2 walked (brc_region_piece_steps)
     std::vector<XAgg> xagg_compact; std::vector<IndelOut> iout_compact;
     enum { XEV_SHARDS = 1024 }; size_t xev_cap = 0;      // the third-allele lists: sub-lists, entries per sub-list
+    uint64_t n_passes = 0;                               // passes the last compute() / compute_n() queued (brc_region_passes)
     Counters h_ctr; bool computed = false;
     bool lists_enqueued = false, lists_host = false;     // the two lists of the last compute are on their way to h_xagg / h_iout; xagg_compact / iout_compact hold them
     Stream stream, stream2;              // the engine's; the text download's (pinned, into one of two host buffers)
@@ -2811,8 +2812,10 @@ class HipBackend : public Backend {
     }
     int compute(brc_timing* t) override {
         HIPCHK(hipSetDevice(device));
+        n_passes = 0;
         for (;;) {
             int rc = enqueue_pass(0); if (rc) return rc;
+            ++n_passes;
             bool again = false;
             if ((rc = finish_passes(&again))) return rc;
             if (!again) break;                           // (a third-allele sub-list was too short: the lists were grown, compute again)
@@ -2830,9 +2833,11 @@ class HipBackend : public Backend {
         int rc = ensure_evsets((size_t)std::min<int>(n, EV_RING)); if (rc) return rc;
         brc_timing acc; memset(&acc, 0, sizeof acc);
         int done = 0;
+        n_passes = 0;
         while (done < n) {
             const int k = std::min<int>(n - done, EV_RING);
             for (int i = 0; i < k; ++i) if ((rc = enqueue_pass((size_t)i))) return rc;
+            n_passes += (uint64_t)k;
             bool again = false;
             if ((rc = finish_passes(&again))) return rc;
             if (again) continue;                         // (lists grown: this ring's passes are repeated)
@@ -2914,6 +2919,7 @@ class HipBackend : public Backend {
     }
 
     void piece_steps(uint64_t* ranged, uint64_t* walked) override { *ranged = compact_on ? h_steps[0] : 0; *walked = compact_on ? h_steps[1] : 0; }
+    void region_passes(uint64_t* passes, uint64_t* cap) override { *passes = n_passes; *cap = (uint64_t)xev_cap; }
     int counts(uint64_t* e, uint64_t* p) override {
         if (!computed) { err = "not computed"; return BRC_E_ARG; }
         if (e) *e = h_ctr.n_events;

@@ -1039,6 +1039,13 @@ int brc_region_piece_steps(brc_engine* e, uint64_t* ranged, uint64_t* walked) {
     return BRC_OK;
 }
 
+int brc_region_passes(brc_engine* e, uint64_t* passes, uint64_t* xev_cap) {
+    if (!e || !passes || !xev_cap) return BRC_E_ARG;
+    if (e->state < 3) return fail(e, BRC_E_ARG, "brc_region_passes before brc_compute");
+    e->be->region_passes(passes, xev_cap);
+    return BRC_OK;
+}
+
 int brc_device_view_get(brc_engine* e, brc_device_view* out) {
     if (!e || !out) return BRC_E_ARG;
     if (e->state < 3) return fail(e, BRC_E_ARG, "brc_device_view_get before brc_compute");

@@ -197,6 +197,8 @@ class Backend {
     virtual int counts(uint64_t* n_events, uint64_t* n_positions) = 0;
     // piece-steps of the last compute: what the tile ranges hold / what the pileup kernel walked (0, 0: not counted — no compaction ran)
     virtual void piece_steps(uint64_t* ranged, uint64_t* walked) { *ranged = 0; *walked = 0; }
+    // how often the last compute() ran the pipeline, and the entries one third-allele sub-list holds now (brc_region_passes)
+    virtual void region_passes(uint64_t* passes, uint64_t* xev_cap) { *passes = 1; *xev_cap = 0; }
     virtual const char* last_error() const = 0;
 };
 

@@ -379,6 +379,12 @@ int  brc_region_counts(brc_engine*, uint64_t* n_events, uint64_t* n_positions);
  * `walked` = the pieces that touch their tile (what it walked).  Both 0 when the region was not compacted. */
 int  brc_region_piece_steps(brc_engine*, uint64_t* ranged, uint64_t* walked);
 
+/* How often the last brc_compute ran the pipeline over its region, and the capacity its third-allele lists have now: `passes` is 1 unless
+ * a list was too short for the region's events (the lists are then grown and the region is computed again: 2), `xev_cap` the entries of
+ * one sub-list (they only grow during an engine's life).  A diagnostic, host code only; a backend without such lists (the oracle) reports
+ * 1 pass and capacity 0. */
+int  brc_region_passes(brc_engine*, uint64_t* passes, uint64_t* xev_cap);
+
 /*
  * Host-side record assembly for the last fetched region: produces the reference's exact stdout text
  * ("chr\tpos\tref\tdepth\t..." lines, one per emitted position) in an engine-owned buffer that stays

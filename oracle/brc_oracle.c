@@ -764,6 +764,13 @@ int brc_region_counts(brc_engine* e, uint64_t* n_events, uint64_t* n_positions) 
     return BRC_OK;
 }
 
+/* no lists, no second pass: the oracle piles every region up once */
+int brc_region_passes(brc_engine* e, uint64_t* passes, uint64_t* xev_cap) {
+    if (!e || !passes || !xev_cap) return BRC_E_ARG;
+    *passes = 1; *xev_cap = 0;
+    return BRC_OK;
+}
+
 int brc_format_region(brc_engine* e, const brc_result* res, const char* chrom, const char** text, size_t* text_len) {
     (void)res;
     if (!e || !chrom || !text) return BRC_E_ARG;

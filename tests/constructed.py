@@ -1,7 +1,8 @@
 """Batches written down by hand (no make_batch, no random batch), shared by the files that test the device pipeline at its own boundaries:
 tests/test_pileup_boundaries.py (k_pileup2), tests/test_annotate_boundaries.py (k_annotate_groups, k_annotate_wave) and
 tests/test_text_boundaries.py (the device's text; run_steps and queue_scenarios below, the latter also run against the reference's
-compiled sources by tests/test_ref_compiled.py)."""
+compiled sources by tests/test_ref_compiled.py) and tests/test_side_paths.py (the third-allele lists, the fold, the indel reduce, the
+counters)."""
 import os
 
 import numpy as np
@@ -34,6 +35,7 @@ class Reads:
         else:
             self.code = ACGT_CODE[ref]; assert self.code.all()
         self.iupac = iupac
+        self.ref = ref
         self.n_ref = len(ref)
         self.rows = []
 
@@ -96,11 +98,12 @@ def ref_of(n):
     return synth.make_ref(np.random.default_rng(20), n)
 
 
-def run_steps(lib, steps, ref=None, chrom="chrS", lib_names=(), clear_queue=False, **opts):
+def run_steps(lib, steps, ref=None, chrom="chrS", lib_names=(), clear_queue=False, observe=None, **opts):
     """Regions on ONE engine, each with a batch and a target of its own (tests/test_text_boundaries.py, tests/test_ref_compiled.py): a step is
     (arrs, (beg0, end)) or a dict(arrs=, region=, tid=0, continues=False, fetch=True).  fetch: only the reads that overlap [beg0 - 1, end)
     are pushed, as the command line fetches them; continues: BRC_OPT_CONTINUES_PREVIOUS (option 6) is set for the step.  Returns the texts
-    and the results, one per step."""
+    and the results, one per step.  observe(eng): called behind every step's text, while the engine still holds the region (counters and
+    other observables that no result carries: tests/test_side_paths.py)."""
     eng = capi.Engine(lib, lib_names=lib_names, **opts)
     texts, results = [], []
     try:
@@ -116,6 +119,8 @@ def run_steps(lib, steps, ref=None, chrom="chrS", lib_names=(), clear_queue=Fals
                 assert not st.get("continues")
             eng.begin_region(st.get("tid", 0), beg0, end, ref); eng.push_reads(arrs)
             results.append(eng.end_region()); texts.append(eng.format_region(chrom))
+            if observe:
+                observe(eng)
             if clear_queue:
                 eng.clear_indel_queue()
         return texts, results

@@ -48,7 +48,8 @@ class SimBackend : public Backend {
     std::vector<Piece> hot; std::vector<PieceRare> rare; std::vector<int32_t> key, reach, prefmax; std::vector<uint32_t> piece_read;
     // the rare record of piece m: stored by K1 only when piece_has_rare(flags), derived from the piece otherwise
     PieceRare rare_of(uint32_t m) const { return piece_has_rare(piece_flags(hot[m])) ? rare[m] : piece_rare_of(c, hot[m]); }
-    std::vector<uint32_t> ncol, depth, slotid, si, unavail; std::vector<float> sf; std::vector<XEv> xev; uint32_t xev_n = 0, xev_bucket_max = 0;
+    std::vector<uint32_t> ncol, depth, slotid, si, unavail; std::vector<float> sf; std::vector<XEv> xev; uint32_t xev_n = 0, xev_bucket_max = 0, xev_sublist_max = 0;
+    uint64_t n_passes = 0;                                    // how often the last compute() walked the tiles (brc_region_passes)
     std::vector<IndelOut> iout;
     // the side tables a text lane reads (brc_core.h: TextAux), in the kernels' layout: folded third-allele records per (tile, library) bucket,
     // reduced indel buckets in their slots
@@ -206,7 +207,9 @@ class SimBackend : public Backend {
                         ", \"range_max\": " + std::to_string(wit.range_max) + ", \"live_max\": " + std::to_string(wit.live_max) + ", \"live_max_read\": " + std::to_string(wit.live_max_read) +
                         ", \"reads_max\": " + std::to_string(wit.reads_max) + ", \"range_starts_behind_next\": " + std::to_string(wit.starts_behind) +
                         ", \"n_reads\": " + std::to_string(c.n_reads) + ", \"ntiles\": " + std::to_string((c.P + TILE - 1) / TILE) + ", \"Lp\": " + std::to_string(c.Lp) +
-                        ", \"pos0\": " + std::to_string(c.pos0) + ", \"P\": " + std::to_string(c.P) + ", \"tile_pieces\": {";
+                        ", \"pos0\": " + std::to_string(c.pos0) + ", \"P\": " + std::to_string(c.P) +
+                        ", \"n_xev\": " + std::to_string(xev_n) + ", \"xev_bucket_max\": " + std::to_string(xev_bucket_max) + ", \"xev_sublist_max\": " + std::to_string(xev_sublist_max) +
+                        ", \"passes\": " + std::to_string(n_passes) + ", \"ibucket_shift\": " + std::to_string(c.ibucket_shift) + ", \"tile_pieces\": {";
         bool first = true;
         for (const auto& kv : wit.tile_pieces) { j += (first ? "\"" : ", \"") + std::to_string(kv.first) + "\": " + std::to_string(kv.second); first = false; }
         j += "}, \"pieces\": {"; first = true;
@@ -264,7 +267,9 @@ class SimBackend : public Backend {
         si.assign((size_t)(Lp * 2 * NI * PS), 0xdeadbeefu); sf.assign((size_t)(Lp * 2 * NF * PS), -1.0f);   // KB must write every plane element
         const char* xc = getenv("BRC_XEV_CAP");                                                            // (test knob: a tiny list exercises the grow-and-recompute path)
         if (xev.empty()) xev.resize(xc ? (size_t)atoi(xc) : 1024);
+        n_passes = 0;
       again:
+        ++n_passes;
         xev_n = 0; wit = Witness();
         Planes pl = {ncol.data(), depth.data(), slotid.data(), si.data(), sf.data(), unavail.data(), xev.data(), &xev_n, (uint32_t)xev.size(), 1u};
         n_events = n_positions = 0; memset(warn, 0, sizeof warn);
@@ -322,6 +327,17 @@ class SimBackend : public Backend {
         }
         if (xev_n > xev.size()) { xev.resize((size_t)xev_n * 2); goto again; }                                 // the list was too short: grow, compute again
         pl_last = pl; have_pl = true;
+        {   // The fullest of the sub-lists the DEVICE would fill with these events.  This is a RESTATEMENT of k_pileup2's shard rule
+            // (brc_engine.hip: xshard = (wg + lib * 257) & (xev_shards - 1), 1024 sub-lists), not a call of it, for PILEUP_WAVES = 4 and
+            // a launch without tile list (wg = tile / 4; with announced windows wg comes from the list slot, and the number says nothing).
+            // The device checks it: tests/test_side_paths.py asserts 2 passes where it exceeds the lists' capacity and 1 where it does not.
+            std::vector<uint32_t> sub(1024, 0);
+            xev_sublist_max = 0;
+            for (uint32_t i = 0; i < xev_n; ++i) {
+                const uint32_t n = ++sub[(size_t)((((xev[i].k >> 6) >> 2) + (xev[i].lib_b >> 8) * 257u) & 1023u)];
+                if (n > xev_sublist_max) xev_sublist_max = n;
+            }
+        }
         {   // k_xev_compact's count / scan / k_xev_scatter / k_xev_fold: the events of every (tile, library) bucket folded in list order
             const int64_t nxb = ntiles * Lp;
             std::vector<uint32_t> cnt((size_t)nxb + 1, 0), off((size_t)nxb + 1, 0);
@@ -498,6 +514,7 @@ class SimBackend : public Backend {
         return BRC_OK;
     }
     int counts(uint64_t* e, uint64_t* p) override { if (e) *e = n_events; if (p) *p = n_positions; return BRC_OK; }
+    void region_passes(uint64_t* passes, uint64_t* cap) override { *passes = n_passes; *cap = xev.size(); }
 };
 
 void* backend_host_alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }      // (no device: plain memory; pushes copy, Backend::adopts_arenas)
@@ -523,6 +540,9 @@ const char* backend_kernel_name(int) { return nullptr; }
 // read has in one tile), "reads_max" (the most reads a wave of k_compact_reads visits for one group of 8 tiles: from the read that holds
 // the group's first slot to the last read whose slots start inside its range), "range_starts_behind_next" (adjacent tiles with
 // lo(t) > lo(t + 1): only trimming does that), and n_reads, ntiles, Lp, pos0, P.
+// For tests/test_side_paths.py, of the third-allele events of the region: "n_xev", "xev_bucket_max" (the most of one (tile, library) bucket,
+// what one lane of k_xev_fold folds), "xev_sublist_max" (the fullest of the 1024 sub-lists the device would fill: a restatement of its
+// shard rule, see compute()), "passes" (the simulator's own, over its one list) and "ibucket_shift".
 extern "C" __attribute__((visibility("default"))) const char* brc_sim_witness(int reset) {
     if (reset) { brc::g_wit_on = true; brc::g_wit_json.clear(); return ""; }
     brc::g_wit_out = "[" + brc::g_wit_json + "]";
