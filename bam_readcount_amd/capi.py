@@ -1003,3 +1003,73 @@ class Runs(_Handle):
     def last_timing(self):
         """kernel seconds (waits for the launches of the last call), bytes asked for and scratch bytes written"""
         return super().last_timing()
+
+
+# ---------------------------------------------------------------- device-side candidate filter (include/brc_vet.h)
+VET_LIB = os.path.join(HERE, "csrc", "libbrc_vet_hip.so")
+VET_EXPORTS = [
+    "brc_vet_create", "brc_vet_destroy", "brc_vet_kind", "brc_vet_last_error", "brc_vet_workspace", "brc_vet_sites", "brc_vet_last_timing",
+]
+VET_MAX_LIB, VET_NVAL = 254, 20
+VET_TESTS = ("DEPTH", "VAR_COUNT", "VAR_FREQ", "STRAND", "VAR_READPOS", "VAR_DIST3", "VAR_BQ", "VAR_MAPQ", "VAR_MMQS", "VAR_RL", "REF_READPOS",
+             "REF_DIST3", "REF_BQ", "REF_MAPQ", "REF_RL", "MMQS_DIFF", "MAPQ_DIFF", "RL_DIFF")          # bit i of a failure word is VET_TESTS[i]
+VET_BIT = {name: 1 << i for i, name in enumerate(VET_TESTS)}
+VET_ALL_TESTS = (1 << len(VET_TESTS)) - 1
+VET_NOT_ASKED, VET_NO_SITE = 1 << 30, 1 << 31
+VET_OUT_OF_RANGE, VET_NOT_ASCENDING = 1, 2
+VET_V_NAMES = ("cv", "cr", "d", "freq", "strand", "mmqs_diff", "mapq_diff", "rl_diff", "var_readpos", "var_dist3", "var_bq", "var_mapq", "var_mmqs",
+               "var_rl", "ref_readpos", "ref_dist3", "ref_bq", "ref_mapq", "ref_mmqs", "ref_rl")         # the columns of vals
+VET_UINTS = ("min_depth", "min_var_count", "freq_num", "freq_den", "min_strand_reads", "strand_num", "strand_den", "min_ref_reads")
+VET_FLOATS = ("min_var_readpos", "min_var_dist3", "min_var_bq", "min_var_mapq", "max_var_mmqs", "min_var_rl", "min_ref_readpos", "min_ref_dist3",
+              "min_ref_bq", "min_ref_mapq", "min_ref_rl", "max_mmqs_diff", "max_mapq_diff", "max_rl_diff")
+VET_DEFAULTS = dict(min_depth=8, min_var_count=4, freq_num=1, freq_den=20, min_strand_reads=5, strand_num=1, strand_den=100, min_ref_reads=2,
+                    min_var_readpos=0.1, min_var_dist3=0.1, min_var_bq=15.0, min_var_mapq=15.0, max_var_mmqs=100.0, min_var_rl=90.0,
+                    min_ref_readpos=0.1, min_ref_dist3=0.1, min_ref_bq=15.0, min_ref_mapq=15.0, min_ref_rl=90.0, max_mmqs_diff=50.0,
+                    max_mapq_diff=50.0, max_rl_diff=0.25)
+
+
+class VetParams(C.Structure):
+    """brc_vet_params (include/brc_vet.h)"""
+    _fields_ = [("lib_on", C.c_void_p), ("tests", C.c_uint32)] + [(k, C.c_uint32) for k in VET_UINTS] + [(k, C.c_float) for k in VET_FLOATS]
+
+
+def vet_params(lib_on=None, tests=VET_ALL_TESTS, **thresholds):
+    """(VetParams, keepalive): lib_on is a sequence of 0 / 1 per library or None (every library is judged), tests a mask of VET_BIT values;
+    thresholds are the members of brc_vet_params by name, VET_DEFAULTS where not given"""
+    unknown = set(thresholds) - set(VET_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown thresholds %r" % sorted(unknown))
+    t = dict(VET_DEFAULTS, **thresholds)
+    p = VetParams(None, tests, *[t[k] for k in VET_UINTS + VET_FLOATS])
+    keepalive = None
+    if lib_on is not None:
+        keepalive = np.ascontiguousarray(lib_on, np.uint8)
+        p.lib_on = keepalive.ctypes.data
+    return p, keepalive
+
+
+class Vet(_Handle):
+    """One handle of a library exporting include/brc_vet.h: the product's libbrc_vet_hip.so (default; raises when it is not built or
+    there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_vet).  sites() takes raw
+    addresses; bam_readcount_amd.tensors.vet() is the interface that allocates and returns arrays."""
+
+    PREFIX, EXPORTS, LIB, NAME = "brc_vet", VET_EXPORTS, VET_LIB, "vet"
+    PROTOS = {"brc_vet_workspace": (C.c_int64, [C.POINTER(DeviceView), C.c_int64]),
+              "brc_vet_sites": (C.c_int, [C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(VetParams), C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_int64] + [C.c_void_p] * 6)}
+
+    def workspace(self, view, n):
+        """bytes of scratch a call over a list of n elements of the view needs"""
+        return int(self.lib.brc_vet_workspace(_ref(view), n))
+
+    def sites_raw(self, view, indels, params, idx, alt, n, dst_stride, fail=None, keep=None, vals=None, status=None, workspace=None, stream=None):
+        """brc_vet_sites as it is: lists, scratch, destinations and the status word are addresses (or None) in memory of the views'
+        kind; returns the code."""
+        return self.lib.brc_vet_sites(self.h, _ref(view), _ref(indels), _ref(params), idx, alt, n, dst_stride, fail, keep, vals, status, workspace, stream)
+
+    def sites(self, view, indels, params, idx, alt, n, dst_stride, **kw):
+        self._check("brc_vet_sites", self.sites_raw(view, indels, params, idx, alt, n, dst_stride, **kw))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last call), bytes asked for and written"""
+        return super().last_timing()

@@ -34,6 +34,12 @@ Where the stretches are — the maximal intervals over which coverage stays in o
 normal, no coverage, reference is N — is answered by runs(): an ascending list of intervals with a class each, found by
 libbrc_runs_hip.so (capi.Runs) over the depth planes; its starts and ends are edges for bins() and masks for select()'s list:
     ok = tensors.runs(eng, capi.Runs(), cuts=(10,), combine="min", keep=(1,), ref_n=True)       # >= 10x in every library, reference known
+
+Between "candidate" and "call" sit the per-allele read-metric tests that false-positive filters run on the thirteen columns — variant
+bucket against reference bucket of the same site.  vet() runs them on a list where it lies, by libbrc_vet_hip.so (capi.Vet), with no
+synchronisation: select -> vet -> sites is a chain of device lists:
+    r = tensors.vet(eng, capi.Vet(), idx=sel["idx"], alt=sel["why"], min_var_count=4, min_var_mapq=20.0)
+    panel = tensors.sites(eng, capi.Panel(), positions=sel["pos"][r["keep"].nonzero()[:, 0]])
 """
 import numpy as np
 
@@ -650,3 +656,133 @@ def runs(engine, runs, *, cuts, combine="min", libs=None, keep=None, ref_n=False
     del keepalive
     off = np.int32(pos0) if v.memory == capi.MEM_HOST else pos0
     return {"n": m, "k0": a, "k1": b, "start": a + off, "end": b + off, "cls": c, "per_class": per, "n_class": n_class}
+
+
+VET_KINDS = ("fail", "keep", "vals")
+
+
+def vet_shapes(n_lib, n):
+    """kind -> (shape, numpy dtype) of vet()'s arrays for a list of n elements: the last axis is the list element"""
+    return {"fail": ((n_lib, 4, n), np.uint32), "keep": ((n,), np.int32), "vals": ((n_lib, 4, capi.VET_NVAL, n), np.float32)}
+
+
+def _vet_tests(tests):
+    if tests is None:
+        return capi.VET_ALL_TESTS
+    if isinstance(tests, (int, np.integer)) and not isinstance(tests, bool):
+        if not 0 <= int(tests) <= capi.VET_ALL_TESTS:
+            raise ValueError("tests: a mask of capi.VET_BIT values")
+        return int(tests)
+    mask = 0
+    for t in ([tests] if isinstance(tests, str) else list(tests)):
+        if t not in capi.VET_BIT:
+            raise ValueError("unknown test %r (one of %r)" % (t, capi.VET_TESTS))
+        mask |= capi.VET_BIT[t]
+    return mask
+
+
+def vet(engine, vet, *, idx, alt=None, libs=None, tests=None, want=VET_KINDS, **thresholds):
+    """The per-allele read-metric tests of include/brc_vet.h on LISTED plane positions of the engine's last computed region: for
+    element j, library l and every base v asked about, the variant bucket's count, strand counts and averages (position in read,
+    distance to the 3' end, base quality, mapping quality, mismatch-quality sum, clipped length) against thresholds and against the
+    reference base's bucket of the same site — exact integer tests, and fp32 tests stated operation by operation.
+
+    idx: plane indices (select()'s "idx"), non-decreasing — a sequence or numpy array, or (HIP libraries) an int32 torch tensor on the
+         engine's device, used where it lies.
+    alt: per element a mask of capi.WHY_A | WHY_C | WHY_G | WHY_T, the bases asked about (select()'s "why"; insertion and deletion bits
+         are ignored), of idx's kind; None: all four.
+    libs: the judged libraries, by the engine's library names or by number (None: all).
+    tests: the tests to run — names of capi.VET_TESTS, or a mask of capi.VET_BIT values (None: all eighteen).
+    thresholds: members of brc_vet_params by name; capi.VET_DEFAULTS where not given: min_depth 8, min_var_count 4, freq 1 / 20,
+         min_strand_reads 5, strand 1 / 100, min_ref_reads 2, min_var_readpos / min_var_dist3 / min_ref_readpos / min_ref_dist3 0.1,
+         min_var_bq / min_var_mapq / min_ref_bq / min_ref_mapq 15, max_var_mmqs 100, min_var_rl / min_ref_rl 90, max_mmqs_diff /
+         max_mapq_diff 50, max_rl_diff 0.25.
+
+    Returns every kind in `want` — "fail": uint32 [n_lib, 4, n] failure words (bit i: capi.VET_TESTS[i]; capi.VET_NOT_ASKED,
+    capi.VET_NO_SITE: nothing judged), "keep": int32 [n] the mask of asked bases that pass every test in SOME judged library, "vals":
+    float32 [n_lib, 4, capi.VET_NVAL, n] the numbers compared (capi.VET_V_NAMES) — plus "status" (one uint32 element in the arrays'
+    memory: capi.VET_OUT_OF_RANGE / VET_NOT_ASCENDING, written by the kernels, not read by this call) and the ints "n", "n_lib", "pos0".
+    With the HIP libraries the arrays are torch tensors on the engine's device, filled on torch's current stream, the scratch comes from
+    torch.empty; with the CPU builds they are numpy arrays.  NOTHING SYNCHRONISES: every size follows from n.  So
+        sel = select(...); r = vet(engine, v, idx=sel["idx"], alt=sel["why"]); k = r["keep"].nonzero()[:, 0]
+        panel = sites(engine, capi.Panel(), positions=sel["pos"][k])
+    runs with device lists throughout.  A list given on the host is checked on the host (non-decreasing, inside the planes); a device
+    tensor is not: "status" tells afterwards.  ValueError for what the library would refuse, before anything is queued."""
+    want = tuple(want)
+    for k in want:
+        if k not in VET_KINDS:
+            raise ValueError("unknown kind %r (one of %r)" % (k, VET_KINDS))
+    mask = _vet_tests(tests)
+    unknown = set(thresholds) - set(capi.VET_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown thresholds %r (capi.VET_DEFAULTS has the names)" % sorted(unknown))
+    t = dict(capi.VET_DEFAULTS, **thresholds)
+    for k in capi.VET_UINTS:
+        t[k] = _u32(t[k], k)
+    if t["freq_den"] == 0 or t["strand_den"] == 0:
+        raise ValueError("a fraction's denominator must not be 0")
+    for k in capi.VET_FLOATS:
+        x = np.float32(t[k])
+        if isinstance(t[k], bool) or not np.isfinite(x):
+            raise ValueError("%s must be a finite number (in fp32)" % k)
+        t[k] = float(x)
+    v, d = engine.device_view(), engine.device_indels()
+    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    if L > capi.VET_MAX_LIB:
+        raise ValueError("the filter takes at most %d libraries" % capi.VET_MAX_LIB)
+    if v.memory not in (capi.MEM_HOST, capi.MEM_DEVICE):
+        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
+    params, keepalive = capi.vet_params(_counted(engine, L, libs), mask, **t)
+    on_device = type(idx).__module__.split(".")[0] == "torch"
+    if alt is not None and (type(alt).__module__.split(".")[0] == "torch") != on_device:
+        raise ValueError("idx and alt must be of one kind: both torch tensors or both host arrays")
+    if on_device:
+        if v.memory != capi.MEM_DEVICE:
+            raise ValueError("a torch tensor of indices needs an engine whose results lie on a GPU")
+        n = int(idx.numel())
+    else:
+        hidx = np.asarray(idx, np.int64).ravel()
+        n = int(hidx.size)
+        if n and (hidx[1:] < hidx[:-1]).any():
+            raise ValueError("the listed indices must not descend")
+        if n and (hidx[0] < 0 or hidx[-1] >= P):
+            raise ValueError("listed indices outside the region's planes [0, %d)" % P)
+        hidx = hidx.astype(np.int32)
+        halt = None
+        if alt is not None:
+            halt = np.asarray(alt, np.int64).ravel()
+            if halt.size != n or ((halt < 0) | (halt >= 2 ** 32)).any():
+                raise ValueError("alt: one mask of capi.WHY_* per listed element")
+            halt = halt.astype(np.uint32)
+    shp = vet_shapes(L, n)
+    wsb = vet.workspace(v, n)
+    if v.memory == capi.MEM_HOST:
+        arrays, ptr, stream = _host_arrays(shp, want, None), (lambda a: a.ctypes.data), None
+        lidx, lalt = hidx, halt
+        status = np.zeros(1, np.uint32)
+        ws = np.empty(max(wsb // 4, 1), np.int32)
+    else:
+        import torch          # (lazily: the package and its CPU route work without torch)
+        dev = torch.device("cuda", int(v.device))
+        if on_device:
+            for a, what, dts in ((idx, "idx", (torch.int32,)), (alt, "alt", (torch.int32, torch.uint32))):
+                if a is not None and (a.dtype not in dts or a.device != dev or a.dim() != 1 or not a.is_contiguous() or int(a.numel()) != n):
+                    raise ValueError("%s must be a contiguous one-dimensional 32-bit integer tensor of idx's length on %s" % (what, dev))
+            lidx, lalt = idx, alt
+        else:
+            lidx = torch.from_numpy(hidx).to(dev)
+            lalt = None if halt is None else torch.from_numpy(halt.view(np.int32)).to(dev)
+        tdt = {np.uint32: torch.uint32, np.int32: torch.int32, np.float32: torch.float32}
+        arrays = {k: torch.empty(shp[k][0], dtype=tdt[shp[k][1]], device=dev) for k in want}
+        ptr = lambda a: a.data_ptr()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+        status = torch.zeros(1, dtype=torch.int32, device=dev).view(torch.uint32)
+        ws = torch.empty(max(wsb // 4, 1), dtype=torch.int32, device=dev)
+    if n:
+        vet.sites(v, d, params, ptr(lidx), None if lalt is None else ptr(lalt), n, n, status=ptr(status), workspace=ptr(ws), stream=stream,
+                  **{k: ptr(arrays[k]) for k in want})
+    del keepalive
+    res = {"pos0": pos0, "n": n, "n_lib": L, "status": status}
+    res.update(arrays)
+    return res
