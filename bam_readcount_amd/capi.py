@@ -20,7 +20,10 @@ F_NAMES = ["sev", "sq2", "snm", "s3p"]
 EXPORTS = [
     "brc_strerror", "brc_last_error", "brc_kernel_name", "brc_engine_kind", "brc_create", "brc_destroy",
     "brc_begin_region", "brc_push_reads", "brc_upload", "brc_compute", "brc_fetch_result", "brc_end_region",
-    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows", "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts", "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned", "brc_region_piece_steps", "brc_region_passes", "brc_device_view_get", "brc_device_indels_get",
+    "brc_clear_indel_queue", "brc_region_counts", "brc_format_region", "brc_format_window", "brc_region_windows",
+    "brc_region_warnings", "brc_window_warnings", "brc_warnings_text", "brc_set_option", "brc_format_region_parts",
+    "brc_set_chrom", "brc_fetch_window", "brc_compute_n", "brc_host_alloc", "brc_host_free", "brc_push_reads_pinned",
+    "brc_region_piece_steps", "brc_region_passes", "brc_device_view_get", "brc_device_indels_get",
 ]
 
 
@@ -121,56 +124,57 @@ def _share_torch_hip_runtime():
             return
 
 
+def _declare(lib, protos, optional=()):
+    """protos {symbol: (restype, argtypes)} onto a loaded library; a missing symbol that is not in `optional` is an AttributeError"""
+    for name, (restype, argtypes) in protos.items():
+        if name in optional and not hasattr(lib, name):
+            continue
+        f = getattr(lib, name)
+        f.restype = restype; f.argtypes = argtypes
+
+
+_H, _I32, _I64 = C.c_void_p, C.c_int32, C.c_int64
+_U64P, _TEXT = C.POINTER(C.c_uint64), [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
+
+
 class Library:
     """One loaded shared library exporting the brc C-ABI."""
+
+    # {symbol: (restype, argtypes)} of the calls of include/brc.h that this module makes; every call that returns a code is a C.c_int
+    PROTOS = {
+        "brc_strerror": (C.c_char_p, [C.c_int]), "brc_last_error": (C.c_char_p, [_H]), "brc_kernel_name": (C.c_char_p, [C.c_int]),
+        "brc_engine_kind": (C.c_char_p, []),
+        "brc_create": (C.c_int, [C.POINTER(Config), C.POINTER(_H)]), "brc_destroy": (None, [_H]),
+        "brc_set_option": (C.c_int, [_H, C.c_int, _I64]), "brc_set_chrom": (C.c_int, [_H, C.c_char_p]),
+        "brc_begin_region": (C.c_int, [_H, _I32, _I32, _I32, C.c_void_p, _I64]),
+        "brc_push_reads": (C.c_int, [_H, C.POINTER(ReadBatch)]), "brc_push_reads_pinned": (C.c_int, [_H, C.POINTER(ReadBatch)]),
+        "brc_host_alloc": (C.c_void_p, [C.c_size_t]), "brc_host_free": (None, [C.c_void_p]),
+        "brc_region_piece_steps": (C.c_int, [_H, _U64P, _U64P]), "brc_region_passes": (C.c_int, [_H, _U64P, _U64P]),
+        "brc_upload": (C.c_int, [_H]),
+        "brc_compute": (C.c_int, [_H, C.POINTER(Timing)]), "brc_compute_n": (C.c_int, [_H, _I32, C.POINTER(Timing)]),
+        "brc_fetch_result": (C.c_int, [_H, C.POINTER(Result)]), "brc_end_region": (C.c_int, [_H, C.POINTER(Result)]),
+        "brc_fetch_window": (C.c_int, [_H, _I32, _I32, C.POINTER(Result)]),
+        "brc_clear_indel_queue": (C.c_int, [_H]), "brc_region_counts": (C.c_int, [_H, _U64P, _U64P]),
+        "brc_format_region": (C.c_int, [_H, C.POINTER(Result), C.c_char_p] + _TEXT),
+        "brc_format_window": (C.c_int, [_H, C.POINTER(Result), C.c_char_p, _I32, _I32, _I32] + _TEXT),
+        "brc_region_warnings": (C.c_int, [_H, C.c_char_p, _I64] + _TEXT),
+        "brc_window_warnings": (C.c_int, [_H, _I32, _I32, _I64] + _TEXT),
+        "brc_warnings_text": (C.c_int, [_H, C.c_char_p, C.c_size_t, _I64, C.POINTER(_I64)] + _TEXT),
+        "brc_region_windows": (C.c_int, [_H, C.POINTER(_I32), C.POINTER(_I32), _I64]),
+        "brc_device_view_get": (C.c_int, [_H, C.POINTER(DeviceView)]), "brc_device_indels_get": (C.c_int, [_H, C.POINTER(DeviceIndels)]),
+    }
+    # what the reference-compiled checker libraries lack: options, the zero-copy (pinned) feed, compute_n, fetch_window, warnings,
+    # windows, device views, piece steps and passes.  Every other symbol of PROTOS must be there, or the load fails.
+    OPTIONAL = {"brc_set_option", "brc_set_chrom", "brc_push_reads_pinned", "brc_host_alloc", "brc_host_free", "brc_region_piece_steps",
+                "brc_region_passes", "brc_compute_n", "brc_fetch_window", "brc_region_warnings", "brc_warnings_text", "brc_window_warnings",
+                "brc_region_windows", "brc_device_view_get", "brc_device_indels_get"}
 
     def __init__(self, path):
         if not os.path.exists(path):
             raise BrcError("brc library not found: %s (run `python __graft_entry__.py` / build() first)" % path)
         self.path = path
         self.lib = L = _load(path)
-        L.brc_strerror.restype = C.c_char_p; L.brc_strerror.argtypes = [C.c_int]
-        L.brc_last_error.restype = C.c_char_p; L.brc_last_error.argtypes = [C.c_void_p]
-        L.brc_kernel_name.restype = C.c_char_p; L.brc_kernel_name.argtypes = [C.c_int]
-        L.brc_engine_kind.restype = C.c_char_p
-        L.brc_create.argtypes = [C.POINTER(Config), C.POINTER(C.c_void_p)]
-        L.brc_destroy.argtypes = [C.c_void_p]; L.brc_destroy.restype = None
-        if hasattr(L, "brc_set_option"):       # (the reference-compiled checker library has no options)
-            L.brc_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int64]
-            L.brc_set_chrom.argtypes = [C.c_void_p, C.c_char_p]
-        L.brc_begin_region.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
-        L.brc_push_reads.argtypes = [C.c_void_p, C.POINTER(ReadBatch)]
-        if hasattr(L, "brc_push_reads_pinned"):   # (zero-copy feed: the engine libraries; the checkers only copy)
-            L.brc_push_reads_pinned.argtypes = [C.c_void_p, C.POINTER(ReadBatch)]
-            L.brc_host_alloc.restype = C.c_void_p; L.brc_host_alloc.argtypes = [C.c_size_t]
-            L.brc_host_free.restype = None; L.brc_host_free.argtypes = [C.c_void_p]
-        if hasattr(L, "brc_region_piece_steps"):
-            L.brc_region_piece_steps.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        if hasattr(L, "brc_region_passes"):
-            L.brc_region_passes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.brc_upload.argtypes = [C.c_void_p]
-        L.brc_compute.argtypes = [C.c_void_p, C.POINTER(Timing)]
-        if hasattr(L, "brc_compute_n"):
-            L.brc_compute_n.argtypes = [C.c_void_p, C.c_int32, C.POINTER(Timing)]
-        L.brc_fetch_result.argtypes = [C.c_void_p, C.POINTER(Result)]
-        L.brc_end_region.argtypes = [C.c_void_p, C.POINTER(Result)]
-        if hasattr(L, "brc_fetch_window"):
-            L.brc_fetch_window.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Result)]
-        L.brc_clear_indel_queue.argtypes = [C.c_void_p]
-        L.brc_region_counts.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-        L.brc_format_region.argtypes = [C.c_void_p, C.POINTER(Result), C.c_char_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
-        if hasattr(L, "brc_region_warnings"):
-            L.brc_region_warnings.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
-            L.brc_warnings_text.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
-        if hasattr(L, "brc_window_warnings"):
-            L.brc_window_warnings.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
-        L.brc_format_window.argtypes = [C.c_void_p, C.POINTER(Result), C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t)]
-        if hasattr(L, "brc_region_windows"):
-            L.brc_region_windows.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64]
-        if hasattr(L, "brc_device_view_get"):   # (the engine libraries; the checkers have dense results only)
-            L.brc_device_view_get.argtypes = [C.c_void_p, C.POINTER(DeviceView)]
-        if hasattr(L, "brc_device_indels_get"):
-            L.brc_device_indels_get.argtypes = [C.c_void_p, C.POINTER(DeviceIndels)]
+        _declare(L, self.PROTOS, self.OPTIONAL)
 
     def kind(self):
         return self.lib.brc_engine_kind().decode()
@@ -181,6 +185,9 @@ class Library:
             s = self.lib.brc_kernel_name(k)
             out.append(s.decode() if s else None)
         return out
+
+
+assert set(Library.PROTOS) <= set(EXPORTS) and Library.OPTIONAL <= set(Library.PROTOS)
 
 
 def load_product():
@@ -435,67 +442,47 @@ class Engine:
         self._check(self.L.lib.brc_format_region(self.h, C.byref(self._res), chrom.encode(), C.byref(p), C.byref(n)))
         return C.string_at(p, n.value)
 
+    def format_region_np(self, chrom):
+        """Text of the last fetched region as a uint8 numpy view of the engine's buffer (no copy; texts above 2 GiB are fine).
+        Valid until the next call on this engine."""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self.L.lib.brc_format_region(self.h, C.byref(self._res), chrom.encode(), C.cast(C.byref(p), C.POINTER(C.c_char_p)), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, np.uint8)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_ubyte)), shape=(n.value,))
 
-def _format_region_np(self, chrom):
-    """Text of the last fetched region as a uint8 numpy view of the engine's buffer (no copy; texts above 2 GiB are fine).
-    Valid until the next call on this engine."""
-    p = C.c_void_p(); n = C.c_size_t()
-    self._check(self.L.lib.brc_format_region(self.h, C.byref(self._res), chrom.encode(), C.cast(C.byref(p), C.POINTER(C.c_char_p)), C.byref(n)))
-    if not n.value:
-        return np.zeros(0, np.uint8)
-    return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_ubyte)), shape=(n.value,))
+    def region_warnings(self, chrom, cap=-1):
+        """Tagged warning events of the last computed region (include/brc.h: brc_region_warnings), bytes."""
+        p = C.c_char_p(); n = C.c_size_t()
+        self._check(self.L.lib.brc_region_warnings(self.h, chrom.encode(), cap, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value)
 
+    def warnings_text(self, events, max_per_type, counts):
+        """ReadWarnings text of an event stream; `counts` (list of 4 ints) are the running per-type counters, updated in place."""
+        c = (C.c_int64 * NWARN)(*counts)
+        p = C.c_char_p(); n = C.c_size_t()
+        self._check(self.L.lib.brc_warnings_text(self.h, events, len(events), max_per_type, c, C.byref(p), C.byref(n)))
+        counts[:] = list(c)
+        return C.string_at(p, n.value)
 
-Engine.format_region_np = _format_region_np
+    def window_warnings(self, vbeg0, vend, cap=-1):
+        """Events of a stand-alone run over [vbeg0,vend) inside the last computed region (site-list planner; no bounds lines)."""
+        p = C.c_char_p(); n = C.c_size_t()
+        self._check(self.L.lib.brc_window_warnings(self.h, vbeg0, vend, cap, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value)
 
+    def format_window(self, chrom, vbeg0, vend, delta):
+        """Text of the sub-window [vbeg0,vend) of the last fetched region, coordinates shifted by -delta (site-list planner)."""
+        p = C.c_char_p(); n = C.c_size_t()
+        self._check(self.L.lib.brc_format_window(self.h, C.byref(self._res), chrom.encode(), vbeg0, vend, delta, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value)
 
-def _region_warnings(self, chrom, cap=-1):
-    """Tagged warning events of the last computed region (include/brc.h: brc_region_warnings), bytes."""
-    p = C.c_char_p(); n = C.c_size_t()
-    self._check(self.L.lib.brc_region_warnings(self.h, chrom.encode(), cap, C.byref(p), C.byref(n)))
-    return C.string_at(p, n.value)
-
-
-def _warnings_text(self, events, max_per_type, counts):
-    """ReadWarnings text of an event stream; `counts` (list of 4 ints) are the running per-type counters, updated in place."""
-    c = (C.c_int64 * NWARN)(*counts)
-    p = C.c_char_p(); n = C.c_size_t()
-    self._check(self.L.lib.brc_warnings_text(self.h, events, len(events), max_per_type, c, C.byref(p), C.byref(n)))
-    counts[:] = list(c)
-    return C.string_at(p, n.value)
-
-
-def _window_warnings(self, vbeg0, vend, cap=-1):
-    """Events of a stand-alone run over [vbeg0,vend) inside the last computed region (site-list planner; no bounds lines)."""
-    p = C.c_char_p(); n = C.c_size_t()
-    self._check(self.L.lib.brc_window_warnings(self.h, vbeg0, vend, cap, C.byref(p), C.byref(n)))
-    return C.string_at(p, n.value)
-
-
-Engine.region_warnings = _region_warnings
-Engine.window_warnings = _window_warnings
-Engine.warnings_text = _warnings_text
-
-
-def _format_window(self, chrom, vbeg0, vend, delta):
-    """Text of the sub-window [vbeg0,vend) of the last fetched region, coordinates shifted by -delta (site-list planner)."""
-    p = C.c_char_p(); n = C.c_size_t()
-    self._check(self.L.lib.brc_format_window(self.h, C.byref(self._res), chrom.encode(), vbeg0, vend, delta, C.byref(p), C.byref(n)))
-    return C.string_at(p, n.value)
-
-
-Engine.format_window = _format_window
-
-
-def _region_windows(self, vbeg0, vend):
-    """Announce the only windows [vbeg0[i], vend[i]) of the open region that will be formatted (site-list planner): the engine
-    piles up only the tiles they touch."""
-    b = np.ascontiguousarray(vbeg0, np.int32); e = np.ascontiguousarray(vend, np.int32)
-    assert b.shape == e.shape and b.ndim == 1
-    self._check(self.L.lib.brc_region_windows(self.h, b.ctypes.data_as(C.POINTER(C.c_int32)), e.ctypes.data_as(C.POINTER(C.c_int32)), b.size))
-
-
-Engine.region_windows = _region_windows
+    def region_windows(self, vbeg0, vend):
+        """Announce the only windows [vbeg0[i], vend[i]) of the open region that will be formatted (site-list planner): the engine
+        piles up only the tiles they touch."""
+        b = np.ascontiguousarray(vbeg0, np.int32); e = np.ascontiguousarray(vend, np.int32)
+        assert b.shape == e.shape and b.ndim == 1
+        self._check(self.L.lib.brc_region_windows(self.h, b.ctypes.data_as(C.POINTER(C.c_int32)), e.ctypes.data_as(C.POINTER(C.c_int32)), b.size))
 
 
 def fetch_overlapping(arrs, ends, lo, hi):
@@ -589,9 +576,7 @@ class _Handle:
                   "_destroy": (None, [C.c_void_p]), "_last_timing": (None, [C.c_void_p] + self.TIMING)}
         protos = {self.PREFIX + k: v for k, v in protos.items()}
         protos.update(self.PROTOS)
-        for name, (restype, argtypes) in protos.items():
-            f = getattr(L, name)
-            f.restype = restype; f.argtypes = argtypes
+        _declare(L, protos)
         self.device = device
         h = C.c_void_p()
         rc = self._call("_create")(device, C.byref(h))

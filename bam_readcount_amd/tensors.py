@@ -41,9 +41,224 @@ synchronisation: select -> vet -> sites is a chain of device lists:
     r = tensors.vet(eng, capi.Vet(), idx=sel["idx"], alt=sel["why"], min_var_count=4, min_var_mapq=20.0)
     panel = tensors.sites(eng, capi.Panel(), positions=sel["pos"][r["keep"].nonzero()[:, 0]])
 """
+from functools import lru_cache, partial
+
 import numpy as np
 
 from . import capi
+
+
+# ------------------------------------------------------------------------------------------------ the memory the results lie in
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+class _Host:
+    """Results in host memory (the CPU builds): numpy arrays, no stream, no torch."""
+    torch = stream = None
+
+    def empty(self, shape, dt):
+        return np.empty(shape, dt)
+
+    def zeros(self, shape, dt):
+        return np.zeros(shape, dt)
+
+    def arange(self, n, dt):
+        return np.arange(n, dtype=dt)
+
+    def ptr(self, a, null_if_empty=False):
+        return None if null_if_empty and not a.size else a.ctypes.data
+
+    def upload(self, a):
+        return a
+
+    def read(self, a):
+        return a.tolist()
+
+    def offset(self, a, k):
+        return a + a.dtype.type(k)            # (the sum keeps the array's dtype)
+
+    def holds(self, x, kind):
+        if _is_torch(x):
+            raise ValueError("a torch tensor of %s needs an engine whose results lie on a GPU" % kind)
+        return False
+
+    def check_out(self, a, k, dt):
+        if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
+            raise ValueError("out[%r] must be a writable C-contiguous numpy array of %s" % (k, np.dtype(dt).name))
+
+
+@lru_cache(None)
+def _torch_dtypes(torch):
+    """THE dtype table: (numpy dtype -> torch dtype, unsigned numpy dtype -> the signed twin it is made as)"""
+    return ({np.int32: torch.int32, np.uint32: torch.uint32, np.int64: torch.int64, np.uint64: torch.uint64, np.float32: torch.float32,
+             np.uint8: torch.uint8}, {np.uint32: torch.int32, np.uint64: torch.int64})
+
+
+class _Device:
+    """Results on cuda:<device> (the HIP libraries): torch tensors, work on torch's current stream of that device.  The one place
+    that imports torch, when a device view is met, and the one place that can make the host wait: read()."""
+
+    def __init__(self, device):
+        import torch          # (lazily: the package and its CPU route work without torch)
+        self.torch = torch
+        self.dtype, self.signed = _torch_dtypes(torch)
+        self.dev = torch.device("cuda", device)
+        self.stream = torch.cuda.current_stream(self.dev).cuda_stream
+
+    def _new(self, make, shape, dt):          # (unsigned 32- and 64-bit tensors: made as their signed twins and viewed, which every torch accepts)
+        if dt in self.signed:
+            return make(shape, dtype=self.signed[dt], device=self.dev).view(self.dtype[dt])
+        return make(shape, dtype=self.dtype[dt], device=self.dev)
+
+    def empty(self, shape, dt):
+        return self._new(self.torch.empty, shape, dt)
+
+    def zeros(self, shape, dt):
+        return self._new(self.torch.zeros, shape, dt)
+
+    def arange(self, n, dt):
+        return self.torch.arange(n, dtype=self.dtype[dt], device=self.dev)
+
+    def ptr(self, a, null_if_empty=False):
+        return None if null_if_empty and not a.numel() else a.data_ptr()
+
+    def upload(self, a):
+        """a host array -> a tensor on the device: one copy from pageable memory, which may wait for the stream"""
+        return self.torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).to(self.dev)
+
+    def read(self, a):
+        """THE WAIT: the host reads device memory — count-then-fill (_sized_by_data) calls this once, nothing else does"""
+        return [a.item()] if a.numel() == 1 else a.cpu().tolist()
+
+    def offset(self, a, k):
+        return a + k
+
+    def holds(self, x, kind):
+        return _is_torch(x)
+
+    def check_list(self, a, what, words, dtypes=(np.int32,), n=None):
+        if a.dtype not in [self.dtype[d] for d in dtypes] or a.device != self.dev or a.dim() != 1 or not a.is_contiguous() or n not in (None, int(a.numel())):
+            raise ValueError("%s must be a contiguous one-dimensional %s on %s" % (what, words, self.dev))
+
+    def check_out(self, a, k, dt):
+        if not isinstance(a, self.torch.Tensor) or a.dtype != self.dtype[dt] or a.device != self.dev or not a.is_contiguous():
+            raise ValueError("out[%r] must be a contiguous %s tensor on %s" % (k, self.dtype[dt], self.dev))
+
+
+def _memory(view, what="brc_device_view"):
+    """the flavour of the memory a view's results lie in"""
+    if view.memory == capi.MEM_HOST:
+        return _Host()
+    if view.memory == capi.MEM_DEVICE:
+        return _Device(int(view.device))
+    raise capi.BrcError("%s of unknown memory kind %d" % (what, view.memory))
+
+
+def _window(view, beg0, end):
+    """[beg0, end) clipped to the view's positions (None: from the first / to the last) -> (k0, n): n positions from plane index k0 on"""
+    P, pos0 = int(view.n_pos), int(view.pos0)
+    lo = pos0 if beg0 is None else max(int(beg0), pos0)
+    hi = pos0 + P if end is None else min(int(end), pos0 + P)
+    lo = min(lo, pos0 + P)
+    n = max(hi - lo, 0)
+    return (lo - pos0 if n else 0), n
+
+
+def _check_want(want, kinds):
+    want = tuple(want)
+    for k in want:
+        if k not in kinds:
+            raise ValueError("unknown kind %r (one of %r)" % (k, kinds))
+    return want
+
+
+def _arrays(mem, shp, want, out=None):
+    """kind -> the array of shp[kind] = (shape, numpy dtype) for every kind in want: the caller's out[kind], validated, or a new one"""
+    arrays = {}
+    for k in want:
+        shape, dt = shp[k]
+        if out is not None and k in out:
+            a = out[k]
+            if tuple(a.shape) != tuple(shape):
+                raise ValueError("out[%r] has shape %r, wanted %r" % (k, tuple(a.shape), tuple(shape)))
+            mem.check_out(a, k, dt)
+        else:
+            a = mem.empty(shape, dt)
+        arrays[k] = a
+    return arrays
+
+
+def _ptrs(mem, arrays, **kw):
+    return {k: mem.ptr(a, **kw) for k, a in arrays.items()}
+
+
+def _scratch(mem, n_bytes):
+    return mem.empty(max(n_bytes // 4, 1), np.int32)
+
+
+def _listed(mem, x, kind, noun, place, lo, hi, closed=False, parse=None):
+    """A caller's ascending list (kind: "positions", "indices", "edges"), where it lies.  A torch tensor stays where it is -> (True,
+    the tensor, its numel): its contents are NOT read, nothing waits; the caller type-checks it (mem.check_list) after its own
+    earlier checks.  Anything else is a host list, checked here — not descending, inside [lo, hi) (closed: [lo, hi]), ValueError
+    otherwise — -> (False, the list as an int64 numpy array, its size), for the caller to upload once, after its last check.
+    noun, place: what the messages call the elements and the bounds."""
+    if mem.holds(x, kind):
+        return True, x, int(x.numel())
+    a = parse(x) if parse else np.asarray(x, np.int64).ravel()
+    if a.size and (a[1:] < a[:-1]).any():
+        raise ValueError("the %s must not descend" % noun)
+    if a.size and (a[0] < lo or (a[-1] > hi if closed else a[-1] >= hi)):
+        raise ValueError("%s outside %s [%d, %d%s" % (noun, place, lo, hi, "]" if closed else ")"))
+    return False, a, int(a.size)
+
+
+def _sized_by_data(mem, call, n_counts, shapes, want, caps, fill_empty=False, **first):
+    """Count-then-fill, for results whose sizes are data — SYNCHRONISES ONCE: call(counts=, **first) asks for the n_counts sizes alone,
+    the host reads them (mem.read: the one wait, as torch.nonzero has one), the arrays `want` of shapes(*sizes) = {destination: (shape,
+    dtype)} are allocated exactly, and call(<caps> = the sizes, <destination> = ...) fills them without another wait — skipped when
+    there is no destination, or (but with fill_empty) no first size.  -> (the sizes, {destination: array})"""
+    counts = mem.zeros(n_counts, np.int32)
+    call(counts=mem.ptr(counts), **first)
+    sizes = [x & 0xFFFFFFFF for x in mem.read(counts)]
+    shp = shapes(*sizes)
+    arrays = {k: mem.empty(*shp[k]) for k in want}
+    if want and (sizes[0] or fill_empty):
+        call(**dict(zip(caps, sizes)), **_ptrs(mem, arrays))
+    return sizes, arrays
+
+
+def _mark_libraries(r, given, value, names, numbers=False):
+    """r[l] = value for every library in `given` — one or a sequence of the engine's library names, with `numbers` library numbers
+    too —, none of them twice.  names: a function that gives the engine's library names, called when the first name is met."""
+    known = None
+    for x in ([given] if isinstance(given, (str, bytes)) else list(given)):
+        if numbers and not isinstance(x, (str, bytes)):
+            if isinstance(x, bool) or int(x) != x or not 0 <= int(x) < r.size:
+                raise ValueError("libs: library names or numbers in [0, %d)" % r.size)
+            l = int(x)
+        else:
+            if known is None:
+                known = names()
+            x = x.decode() if isinstance(x, bytes) else x
+            if x not in known:
+                raise ValueError("%r is not a library of the engine (%r)" % (x, known))
+            l = known.index(x)
+        if r[l]:
+            raise ValueError("library %r is named twice" % (x,))
+        r[l] = value
+
+
+def _library_names(engine, n_lib, who):
+    """the engine's library names, one per library; who: the subject of the message ("libs names")"""
+    names = [b.decode() for b in engine._names]
+    if len(names) != n_lib:
+        raise ValueError("%s libraries: the engine reports one set of counts for all of them" % who)
+    return names
+
+
+# ------------------------------------------------------------------------------------------------ the seven entry points
 
 KINDS = ("istat", "fstat", "metrics", "depth", "ncol", "unavail")
 DEFAULT_WANT = ("istat", "fstat", "metrics", "depth", "ncol")
@@ -66,69 +281,15 @@ def region(engine, dense, beg0=None, end=None, want=DEFAULT_WANT, out=None):
     and "n_lib".
     out: a dict of arrays to fill instead of allocating (same shapes, dtypes, device; contiguous).
     """
-    want = tuple(want)
-    for k in want:
-        if k not in KINDS:
-            raise ValueError("unknown kind %r (one of %r)" % (k, KINDS))
+    want = _check_want(want, KINDS)
     v = engine.device_view()
-    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
-    lo = pos0 if beg0 is None else max(int(beg0), pos0)
-    hi = pos0 + P if end is None else min(int(end), pos0 + P)
-    lo = min(lo, pos0 + P)
-    n = max(hi - lo, 0)
-    k0 = lo - pos0 if n else 0
-    res = {"pos0": pos0, "first": pos0 + k0, "n": n, "n_lib": L}
-    shp = shapes(L, n)
-    if v.memory == capi.MEM_HOST:
-        arrays, ptr, stream = _host_arrays(shp, want, out), (lambda a: a.ctypes.data), None
-    elif v.memory == capi.MEM_DEVICE:
-        arrays, ptr, stream = _torch_arrays(shp, want, out, int(v.device))
-    else:
-        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
-    if n and want:
-        dense.expand(v, k0, n, n, stream=stream, **{k: ptr(arrays[k]) for k in want})
-    res.update(arrays)
-    return res
-
-
-def _check_out(a, shape, what):
-    if tuple(a.shape) != tuple(shape):
-        raise ValueError("out[%r] has shape %r, wanted %r" % (what, tuple(a.shape), tuple(shape)))
-
-
-def _host_arrays(shp, want, out):
-    arrays = {}
-    for k in want:
-        shape, dt = shp[k]
-        if out is not None and k in out:
-            a = out[k]
-            _check_out(a, shape, k)
-            if not isinstance(a, np.ndarray) or a.dtype != dt or not a.flags["C_CONTIGUOUS"] or not a.flags["WRITEABLE"]:
-                raise ValueError("out[%r] must be a writable C-contiguous numpy array of %s" % (k, np.dtype(dt).name))
-        else:
-            a = np.empty(shape, dt)
-        arrays[k] = a
-    return arrays
-
-
-def _torch_arrays(shp, want, out, device):
-    import torch          # (lazily: the package and its CPU route work without torch)
-    dev = torch.device("cuda", device)
-    tdt = {np.uint32: torch.uint32, np.float32: torch.float32}
-    arrays = {}
-    for k in want:
-        shape, dt = shp[k]
-        if out is not None and k in out:
-            a = out[k]
-            _check_out(a, shape, k)
-            if not isinstance(a, torch.Tensor) or a.dtype != tdt[dt] or a.device != dev or not a.is_contiguous():
-                raise ValueError("out[%r] must be a contiguous %s tensor on %s" % (k, tdt[dt], dev))
-        else:
-            a = torch.empty(shape, dtype=tdt[dt], device=dev)
-        arrays[k] = a
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream().cuda_stream
-    return arrays, (lambda a: a.data_ptr()), stream
+    pos0, L = int(v.pos0), int(v.n_lib)
+    k0, n = _window(v, beg0, end)
+    mem = _memory(v)
+    arrays = _arrays(mem, shapes(L, n), want, out)
+    if n and want:                                                # NOTHING SYNCHRONISES: every size is known on the host
+        dense.expand(v, k0, n, n, stream=mem.stream, **_ptrs(mem, arrays))
+    return dict({"pos0": pos0, "first": pos0 + k0, "n": n, "n_lib": L}, **arrays)
 
 
 INDEL_KINDS = capi.INDEL_DESTS
@@ -155,48 +316,16 @@ def indels(engine, indels, beg0=None, end=None, want=INDEL_DEFAULT_WANT):
     SYNCHRONISES ONCE: the table's sizes are data.  A first gather asks for the two counts alone, the host reads them (as
     torch.nonzero does), then the arrays are allocated exactly and a second gather fills them without another wait.
     """
-    want = tuple(want)
-    for k in want:
-        if k not in INDEL_KINDS:
-            raise ValueError("unknown kind %r (one of %r)" % (k, INDEL_KINDS))
+    want = _check_want(want, INDEL_KINDS)
     v = engine.device_indels()
-    P, pos0 = int(v.n_pos), int(v.pos0)
-    lo = pos0 if beg0 is None else max(int(beg0), pos0)
-    hi = pos0 + P if end is None else min(int(end), pos0 + P)
-    lo = min(lo, pos0 + P)
-    n = max(hi - lo, 0)
-    k0 = lo - pos0 if n else 0
+    k0, n = _window(v, beg0, end)
     wsb = indels.workspace(v, n)
-    if v.memory == capi.MEM_HOST:
-        def empty(shape, dt):
-            return np.empty(shape, dt)
-        ptr, stream = (lambda a: a.ctypes.data), None
-        ws = np.empty(max(wsb // 4, 1), np.uint32)
-        counts = np.zeros(2, np.uint32)
-    elif v.memory == capi.MEM_DEVICE:
-        import torch          # (lazily: the package and its CPU route work without torch)
-        dev = torch.device("cuda", int(v.device))
-        tdt = {np.int32: torch.int32, np.uint32: torch.uint32, np.float32: torch.float32, np.uint8: torch.uint8}
-
-        def empty(shape, dt):
-            return torch.empty(shape, dtype=tdt[dt], device=dev)
-        ptr = lambda a: a.data_ptr()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-        ws = torch.empty(max(wsb // 4, 1), dtype=torch.int32, device=dev)
-        counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    else:
-        raise capi.BrcError("brc_device_indels of unknown memory kind %d" % v.memory)
-    indels.gather(v, k0, n, workspace=ptr(ws), workspace_bytes=wsb, counts=ptr(counts), stream=stream)
-    m, nbytes = (int(x) & 0xFFFFFFFF for x in (counts.tolist() if v.memory == capi.MEM_HOST else counts.cpu().tolist()))      # the one wait
-    shp = indel_shapes(m, nbytes)
-    arrays = {k: empty(*shp[k]) for k in want}
-    if want:
-        indels.gather(v, k0, n, workspace=ptr(ws), workspace_bytes=wsb, cap=m, alleles_cap=nbytes, stream=stream,
-                      **{k: ptr(arrays[k]) for k in want})
-    res = {"m": m, "first": pos0 + k0, "n": n}
-    res.update(arrays)
-    return res
+    mem = _memory(v, "brc_device_indels")
+    ws = _scratch(mem, wsb)
+    # ONE WAIT: the two sizes are data
+    (m, nbytes), arrays = _sized_by_data(mem, partial(indels.gather, v, k0, n, workspace=mem.ptr(ws), workspace_bytes=wsb, stream=mem.stream), 2,
+                                         indel_shapes, want, ("cap", "alleles_cap"), fill_empty=True)
+    return dict({"m": m, "first": int(v.pos0) + k0, "n": n}, **arrays)
 
 
 def _window_positions(windows):
@@ -237,62 +366,39 @@ def sites(engine, panel, positions=None, windows=None, want=DEFAULT_WANT, out=No
     """
     if (positions is None) == (windows is None):
         raise ValueError("give exactly one of positions and windows")
-    want = tuple(want)
-    for k in want:
-        if k not in KINDS:
-            raise ValueError("unknown kind %r (one of %r)" % (k, KINDS))
+    want = _check_want(want, KINDS)
     v = engine.device_view()
     P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
-    if v.memory not in (capi.MEM_HOST, capi.MEM_DEVICE):
-        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
-    on_device = type(positions).__module__.split(".")[0] == "torch"
-    if on_device:
-        if v.memory != capi.MEM_DEVICE:
-            raise ValueError("a torch tensor of positions needs an engine whose results lie on a GPU")
-        n = int(positions.numel())
+    mem = _memory(v)
+    site = None
+    if windows is not None:
+        positions, site = _window_positions(windows)
+    # NOTHING SYNCHRONISES for a device tensor (used where it lies, unread); a host list is checked here and uploaded once below
+    here, pos, n = _listed(mem, positions, "positions", "listed positions", "the region's planes", pos0, pos0 + P)
+    arrays = _arrays(mem, shapes(L, n), want, out)
+    if here:
+        mem.check_list(pos, "positions", "int32 tensor")
+        idx, lpos, lsite = mem.offset(pos, -pos0), pos, mem.arange(n, np.int32)
     else:
-        pos, site = _window_positions(windows) if windows is not None else (np.asarray(positions, np.int64).ravel(), None)
-        n = int(pos.size)
-        if n and (pos[1:] < pos[:-1]).any():
-            raise ValueError("the listed positions must not descend")
-        if n and (pos[0] < pos0 or pos[-1] >= pos0 + P):
-            raise ValueError("listed positions outside the region's planes [%d, %d)" % (pos0, pos0 + P))
-        if site is None:
-            site = np.arange(n)
-        host = np.stack([pos - pos0, pos, site]).astype(np.int32)          # idx, pos, site: one upload
-    shp = shapes(L, n)
-    if v.memory == capi.MEM_HOST:
-        arrays, ptr, stream = _host_arrays(shp, want, out), (lambda a: a.ctypes.data), None
-        idx, lpos, lsite = host[0], host[1], host[2]
-        status = np.zeros(1, np.uint32)
-    else:
-        arrays, ptr, stream = _torch_arrays(shp, want, out, int(v.device))
-        import torch
-        dev = torch.device("cuda", int(v.device))
-        if on_device:
-            if positions.dtype != torch.int32 or positions.device != dev or positions.dim() != 1 or not positions.is_contiguous():
-                raise ValueError("positions must be a contiguous one-dimensional int32 tensor on %s" % dev)
-            lpos, idx, lsite = positions, positions - pos0, torch.arange(n, dtype=torch.int32, device=dev)
-        else:
-            idx, lpos, lsite = torch.from_numpy(host).to(dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev).view(torch.uint32)
+        idx, lpos, lsite = mem.upload(np.stack([pos - pos0, pos, np.arange(n) if site is None else site]).astype(np.int32))       # one upload
+    status = mem.zeros(1, np.uint32)
     if n:
-        panel.gather(v, ptr(idx), n, n, status=ptr(status), stream=stream, **{k: ptr(arrays[k]) for k in want})
-    res = {"pos0": pos0, "n": n, "n_lib": L, "pos": lpos, "site": lsite, "status": status}
-    res.update(arrays)
+        panel.gather(v, mem.ptr(idx), n, n, status=mem.ptr(status), stream=mem.stream, **_ptrs(mem, arrays))
+    res = dict({"pos0": pos0, "n": n, "n_lib": L, "pos": lpos, "site": lsite, "status": status}, **arrays)
     if indels is not None:
-        res["indels"] = _listed_indels(engine, indels, lpos, n, pos0)
+        res["indels"] = _listed_indels(mem, engine, indels, lpos, n, pos0)
     return res
 
 
-def _listed_indels(engine, indels_lib, listed, n, pos0):
+def _listed_indels(mem, engine, indels_lib, listed, n, pos0):
     """indels() over [min, max] of the listed positions, reduced to the records whose position is listed, plus "j": searchsorted and
     index arithmetic in numpy / torch, no kernel of its own."""
     if n == 0:
         t = indels(engine, indels_lib, beg0=pos0, end=pos0)          # (an empty window: no record)
     else:
         t = indels(engine, indels_lib, beg0=int(listed.min()), end=int(listed.max()) + 1)
-    if isinstance(t["pos"], np.ndarray):
+    torch = mem.torch
+    if torch is None:
         def take(a, sel):
             return a[..., sel]
         rep, cat = np.repeat, np.concatenate
@@ -302,8 +408,7 @@ def _listed_indels(engine, indels_lib, listed, n, pos0):
         jj = np.searchsorted(listed, t["pos"], side="left") if n else np.zeros(0, np.int64)
         sel = np.nonzero((jj < n) & (listed[np.minimum(jj, n - 1)] == t["pos"]))[0] if n else jj
     else:
-        import torch
-        dev = t["pos"].device
+        dev = mem.dev
 
         def take(a, sel):             # (torch indexes no unsigned 32-bit tensors: through their int32 view)
             if a.dtype == torch.uint32:
@@ -340,18 +445,10 @@ def _roles(engine, n_lib, role, case, control):
             raise ValueError("role: one of 0 (ignore), 1 (case), 2 (control) per library, %d of them" % n_lib)
         r = r.astype(np.uint8)
     else:
-        names = [b.decode() for b in engine._names]
-        if len(names) != n_lib:
-            raise ValueError("case / control name libraries: the engine reports one set of counts for all of them")
+        names = _library_names(engine, n_lib, "case / control name")
         r = np.zeros(n_lib, np.uint8)
-        for value, given in ((capi.ROLE_CASE, case), (capi.ROLE_CONTROL, control)):
-            for name in ([given] if isinstance(given, (str, bytes)) else list(given or [])):
-                name = name.decode() if isinstance(name, bytes) else name
-                if name not in names:
-                    raise ValueError("%r is not a library of the engine (%r)" % (name, names))
-                if r[names.index(name)]:
-                    raise ValueError("library %r is named twice" % name)
-                r[names.index(name)] = value
+        _mark_libraries(r, [] if case is None else case, capi.ROLE_CASE, lambda: names)
+        _mark_libraries(r, [] if control is None else control, capi.ROLE_CONTROL, lambda: names)
     if not (r == capi.ROLE_CASE).any():
         raise ValueError("no case library")
     return r
@@ -395,43 +492,21 @@ def select(engine, select, *, role=None, case=None, control=None, snv=True, inde
     if _u32(min_alt, "min_alt") == 0:
         raise ValueError("min_alt must be at least 1")
     v, d = engine.device_view(), engine.device_indels()
-    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    pos0, L = int(v.pos0), int(v.n_lib)
     if L > capi.SELECT_MAX_LIB:
         raise ValueError("the selector takes at most %d libraries" % capi.SELECT_MAX_LIB)
     roles = _roles(engine, L, role, case, control)
     params, keep = capi.select_params(roles, flags, _u32(min_depth, "min_depth"), int(min_alt), frac, _u32(ctl_min_depth, "ctl_min_depth"),
                                       _u32(ctl_max_alt, "ctl_max_alt"), cfrac)
-    lo = pos0 if beg0 is None else max(int(beg0), pos0)
-    hi = pos0 + P if end is None else min(int(end), pos0 + P)
-    lo = min(lo, pos0 + P)
-    n = max(hi - lo, 0)
-    k0 = lo - pos0 if n else 0
+    k0, n = _window(v, beg0, end)
     wsb = select.workspace(v, d, n)
-    if v.memory == capi.MEM_HOST:
-        def empty(m):
-            return np.empty(m, np.int32)
-        ptr, stream = (lambda a: a.ctypes.data), None
-        counts = np.zeros(1, np.int32)
-    elif v.memory == capi.MEM_DEVICE:
-        import torch          # (lazily: the package and its CPU route work without torch)
-        dev = torch.device("cuda", int(v.device))
-
-        def empty(m):
-            return torch.empty(m, dtype=torch.int32, device=dev)
-        ptr = lambda a: a.data_ptr()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-        counts = torch.zeros(1, dtype=torch.int32, device=dev)
-    else:
-        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
-    ws = empty(max(wsb // 4, 1))
-    select.sites(v, d, params, k0, n, counts=ptr(counts), workspace=ptr(ws), stream=stream)
-    m = int(counts[0]) & 0xFFFFFFFF                                       # the one wait
-    idx, why = empty(m), empty(m)
-    if m:
-        select.sites(v, d, params, k0, n, cap=m, idx=ptr(idx), why=ptr(why), workspace=ptr(ws), stream=stream)
+    mem = _memory(v)
+    ws = _scratch(mem, wsb)
+    # ONE WAIT: the list's length is data
+    (m,), got = _sized_by_data(mem, partial(select.sites, v, d, params, k0, n, workspace=mem.ptr(ws), stream=mem.stream), 1,
+                               lambda m: {"idx": ((m,), np.int32), "why": ((m,), np.int32)}, ("idx", "why"), ("cap",))
     del keep
-    return {"idx": idx, "pos": idx + np.int32(pos0) if v.memory == capi.MEM_HOST else idx + pos0, "why": why, "n": m, "first": pos0 + k0, "pos0": pos0}
+    return {"idx": got["idx"], "pos": mem.offset(got["idx"], pos0), "why": got["why"], "n": m, "first": pos0 + k0, "pos0": pos0}
 
 
 BIN_KINDS = ("sums", "covered", "hist")
@@ -463,10 +538,7 @@ def bins(engine, bins, *, width=None, edges=None, thresholds=(), hist=0, beg0=No
     operators on unsigned types).
     With the HIP libraries the arrays are torch tensors on the engine's device, filled on torch's current stream; every size is
     known on the host, so NOTHING SYNCHRONISES.  With the CPU builds they are numpy arrays."""
-    want = tuple(want)
-    for k in want:
-        if k not in BIN_KINDS:
-            raise ValueError("unknown kind %r (one of %r)" % (k, BIN_KINDS))
+    want = _check_want(want, BIN_KINDS)
     if (width is None) == (edges is None):
         raise ValueError("give exactly one of width and edges")
     thr = [_u32(t, "a threshold") for t in thresholds]
@@ -478,67 +550,42 @@ def bins(engine, bins, *, width=None, edges=None, thresholds=(), hist=0, beg0=No
     if width is not None and (isinstance(width, bool) or int(width) != width or int(width) < 1):
         raise ValueError("width must be a positive integer")
     v, d = engine.device_view(), engine.device_indels()
-    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
-    if v.memory not in (capi.MEM_HOST, capi.MEM_DEVICE):
-        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
-    lo = pos0 if beg0 is None else max(int(beg0), pos0)
-    hi = pos0 + P if end is None else min(int(end), pos0 + P)
-    lo = min(lo, pos0 + P)
-    n = max(hi - lo, 0)
-    k0 = lo - pos0 if n else 0
+    pos0, L = int(v.pos0), int(v.n_lib)
+    mem = _memory(v)
+    k0, n = _window(v, beg0, end)
     first = pos0 + k0
-    on_device = edges is not None and type(edges).__module__.split(".")[0] == "torch"
-    host_edges = None
     if width is not None:
         n_bins = (n + int(width) - 1) // int(width)
-    elif on_device:
-        if v.memory != capi.MEM_DEVICE:
-            raise ValueError("a torch tensor of edges needs an engine whose results lie on a GPU")
-        n_bins = int(edges.numel()) - 1
     else:
-        e = np.asarray(edges)
-        if e.ndim != 1 or e.size < 1 or (e.size and (e.astype(np.int64) != e).any()):
-            raise ValueError("edges: a one-dimensional list of at least one integer position")
-        e = e.astype(np.int64)
-        if (e[1:] < e[:-1]).any():
-            raise ValueError("the edges must not descend")
-        if e[0] < first or e[-1] > first + n:
-            raise ValueError("edges outside the window [%d, %d]" % (first, first + n))
-        host_edges = (e - pos0).astype(np.int32)
-        n_bins = int(e.size) - 1
-    if n_bins < 0:
-        raise ValueError("edges: at least one position")
-    shp = {"sums": (L, capi.BINS_NSUM, n_bins), "covered": (L, len(thr), n_bins), "hist": (L, n_hist)}
-    if v.memory == capi.MEM_HOST:
-        arrays = {k: np.empty(shp[k], np.uint64) for k in want}
-        ptr, stream = (lambda a: a.ctypes.data if a.size else None), None
-        status = np.zeros(1, np.uint32)
-        idx = host_edges
-        start = first + np.arange(n_bins, dtype=np.int64) * int(width) if width is not None else None
-    else:
-        import torch          # (lazily: the package and its CPU route work without torch)
-        dev = torch.device("cuda", int(v.device))
-        arrays = {k: torch.empty(shp[k], dtype=torch.int64, device=dev).view(torch.uint64) for k in want}
-        ptr = lambda a: a.data_ptr() if a.numel() else None
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-        status = torch.zeros(1, dtype=torch.int32, device=dev).view(torch.uint32)
-        if on_device:
-            if edges.dtype != torch.int32 or edges.device != dev or edges.dim() != 1 or not edges.is_contiguous():
-                raise ValueError("edges must be a contiguous one-dimensional int32 tensor on %s" % dev)
-            idx = edges - pos0
-        else:
-            idx = torch.from_numpy(host_edges).to(dev) if host_edges is not None else None
-        start = first + torch.arange(n_bins, dtype=torch.int64, device=dev) * int(width) if width is not None else None
-    params = capi.bins_params(int(width) if width is not None else 0, ptr(idx) if idx is not None else None, n_bins if width is None else 0, thr, n_hist)
-    if width is None and params.edges is None:
-        raise ValueError("edges: at least one position")
-    bins.reduce(v, d, params, k0, n, n_bins, status=ptr(status), stream=stream, **{k: ptr(arrays[k]) for k in want})
+        # NOTHING SYNCHRONISES for a device tensor (used where it lies, unread); a host list is checked here and uploaded once below
+        here, e, n_edges = _listed(mem, edges, "edges", "edges", "the window", first, first + n, closed=True, parse=_edge_list)
+        n_bins = n_edges - 1
+        if n_bins < 0:
+            raise ValueError("edges: at least one position")
+    arrays = _arrays(mem, {"sums": ((L, capi.BINS_NSUM, n_bins), np.uint64), "covered": ((L, len(thr), n_bins), np.uint64),
+                           "hist": ((L, n_hist), np.uint64)}, want)
+    status = mem.zeros(1, np.uint32)
+    if width is None and here:
+        mem.check_list(e, "edges", "int32 tensor")
     res = {"n_bins": n_bins, "first": first, "n": n, "n_lib": L, "pos0": pos0, "status": status}
-    if start is not None:
-        res["start"] = start
+    if width is not None:
+        res["start"] = first + mem.arange(n_bins, np.int64) * int(width)
+        params = capi.bins_params(int(width), None, 0, thr, n_hist)
+    else:
+        idx = mem.offset(e, -pos0) if here else mem.upload((e - pos0).astype(np.int32))
+        params = capi.bins_params(0, mem.ptr(idx, null_if_empty=True), n_bins, thr, n_hist)
+        if params.edges is None:
+            raise ValueError("edges: at least one position")
+    bins.reduce(v, d, params, k0, n, n_bins, status=mem.ptr(status), stream=mem.stream, **_ptrs(mem, arrays, null_if_empty=True))
     res.update(arrays)
     return res
+
+
+def _edge_list(edges):
+    e = np.asarray(edges)
+    if e.ndim != 1 or e.size < 1 or (e.size and (e.astype(np.int64) != e).any()):
+        raise ValueError("edges: a one-dimensional list of at least one integer position")
+    return e.astype(np.int64)
 
 
 RUNS_COMBINE = {"min": capi.RUNS_MIN, "max": capi.RUNS_MAX, "sum": capi.RUNS_SUM}
@@ -552,24 +599,7 @@ def _counted(engine, n_lib, libs):
     if not given:
         raise ValueError("no library is counted")
     r = np.zeros(n_lib, np.uint8)
-    names = None
-    for x in given:
-        if isinstance(x, (str, bytes)):
-            if names is None:
-                names = [b.decode() for b in engine._names]
-                if len(names) != n_lib:
-                    raise ValueError("libs names libraries: the engine reports one set of counts for all of them")
-            x = x.decode() if isinstance(x, bytes) else x
-            if x not in names:
-                raise ValueError("%r is not a library of the engine (%r)" % (x, names))
-            l = names.index(x)
-        else:
-            if isinstance(x, bool) or int(x) != x or not 0 <= int(x) < n_lib:
-                raise ValueError("libs: library names or numbers in [0, %d)" % n_lib)
-            l = int(x)
-        if r[l]:
-            raise ValueError("library %r is named twice" % (x,))
-        r[l] = 1
+    _mark_libraries(r, given, 1, partial(_library_names, engine, n_lib, "libs names"), numbers=True)
     return r
 
 
@@ -612,7 +642,7 @@ def runs(engine, runs, *, cuts, combine="min", libs=None, keep=None, ref_n=False
         if not mask:
             raise ValueError("keep is empty: no class would be returned")
     v = engine.device_view()
-    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    pos0, L = int(v.pos0), int(v.n_lib)
     if L > capi.RUNS_MAX_LIB:
         raise ValueError("runs takes at most %d libraries" % capi.RUNS_MAX_LIB)
     d = None
@@ -622,40 +652,17 @@ def runs(engine, runs, *, cuts, combine="min", libs=None, keep=None, ref_n=False
         except capi.BrcError as e:
             raise ValueError("ref_n needs the engine's indels view, which carries the reference: %s" % e)
     params, keepalive = capi.runs_params(cut, RUNS_COMBINE[combine], _counted(engine, L, libs), mask, capi.RUNS_REF_N if ref_n else 0)
-    lo = pos0 if beg0 is None else max(int(beg0), pos0)
-    hi = pos0 + P if end is None else min(int(end), pos0 + P)
-    lo = min(lo, pos0 + P)
-    n = max(hi - lo, 0)
-    k0 = lo - pos0 if n else 0
+    k0, n = _window(v, beg0, end)
     wsb = runs.workspace(n)
-    if v.memory == capi.MEM_HOST:
-        def empty(m):
-            return np.empty(m, np.int32)
-        ptr, stream = (lambda a: a.ctypes.data), None
-        counts = np.zeros(1, np.int32)
-        per = np.zeros(n_class, np.uint64)
-    elif v.memory == capi.MEM_DEVICE:
-        import torch          # (lazily: the package and its CPU route work without torch)
-        dev = torch.device("cuda", int(v.device))
-
-        def empty(m):
-            return torch.empty(m, dtype=torch.int32, device=dev)
-        ptr = lambda a: a.data_ptr()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-        counts = torch.zeros(1, dtype=torch.int32, device=dev)
-        per = torch.zeros(n_class, dtype=torch.int64, device=dev).view(torch.uint64)
-    else:
-        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
-    ws = empty(max(wsb // 4, 1))
-    runs.find(v, d, params, k0, n, counts=ptr(counts), per_class=ptr(per), workspace=ptr(ws), stream=stream)
-    m = int(counts[0]) & 0xFFFFFFFF                                       # the one wait
-    a, b, c = empty(m), empty(m), empty(m)
-    if m:
-        runs.find(v, d, params, k0, n, cap=m, start=ptr(a), end=ptr(b), cls=ptr(c), workspace=ptr(ws), stream=stream)
+    mem = _memory(v)
+    ws, per = _scratch(mem, wsb), mem.zeros(n_class, np.uint64)
+    # ONE WAIT: the list's length is data
+    (m,), got = _sized_by_data(mem, partial(runs.find, v, d, params, k0, n, workspace=mem.ptr(ws), stream=mem.stream), 1,
+                               lambda m: dict.fromkeys(("start", "end", "cls"), ((m,), np.int32)), ("start", "end", "cls"), ("cap",),
+                               per_class=mem.ptr(per))
     del keepalive
-    off = np.int32(pos0) if v.memory == capi.MEM_HOST else pos0
-    return {"n": m, "k0": a, "k1": b, "start": a + off, "end": b + off, "cls": c, "per_class": per, "n_class": n_class}
+    a, b = got["start"], got["end"]
+    return {"n": m, "k0": a, "k1": b, "start": mem.offset(a, pos0), "end": mem.offset(b, pos0), "cls": got["cls"], "per_class": per, "n_class": n_class}
 
 
 VET_KINDS = ("fail", "keep", "vals")
@@ -708,10 +715,7 @@ def vet(engine, vet, *, idx, alt=None, libs=None, tests=None, want=VET_KINDS, **
         panel = sites(engine, capi.Panel(), positions=sel["pos"][k])
     runs with device lists throughout.  A list given on the host is checked on the host (non-decreasing, inside the planes); a device
     tensor is not: "status" tells afterwards.  ValueError for what the library would refuse, before anything is queued."""
-    want = tuple(want)
-    for k in want:
-        if k not in VET_KINDS:
-            raise ValueError("unknown kind %r (one of %r)" % (k, VET_KINDS))
+    want = _check_want(want, VET_KINDS)
     mask = _vet_tests(tests)
     unknown = set(thresholds) - set(capi.VET_DEFAULTS)
     if unknown:
@@ -730,59 +734,29 @@ def vet(engine, vet, *, idx, alt=None, libs=None, tests=None, want=VET_KINDS, **
     P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
     if L > capi.VET_MAX_LIB:
         raise ValueError("the filter takes at most %d libraries" % capi.VET_MAX_LIB)
-    if v.memory not in (capi.MEM_HOST, capi.MEM_DEVICE):
-        raise capi.BrcError("brc_device_view of unknown memory kind %d" % v.memory)
+    mem = _memory(v)
     params, keepalive = capi.vet_params(_counted(engine, L, libs), mask, **t)
-    on_device = type(idx).__module__.split(".")[0] == "torch"
-    if alt is not None and (type(alt).__module__.split(".")[0] == "torch") != on_device:
+    if alt is not None and _is_torch(alt) != _is_torch(idx):
         raise ValueError("idx and alt must be of one kind: both torch tensors or both host arrays")
-    if on_device:
-        if v.memory != capi.MEM_DEVICE:
-            raise ValueError("a torch tensor of indices needs an engine whose results lie on a GPU")
-        n = int(idx.numel())
-    else:
-        hidx = np.asarray(idx, np.int64).ravel()
-        n = int(hidx.size)
-        if n and (hidx[1:] < hidx[:-1]).any():
-            raise ValueError("the listed indices must not descend")
-        if n and (hidx[0] < 0 or hidx[-1] >= P):
-            raise ValueError("listed indices outside the region's planes [0, %d)" % P)
-        hidx = hidx.astype(np.int32)
-        halt = None
-        if alt is not None:
-            halt = np.asarray(alt, np.int64).ravel()
-            if halt.size != n or ((halt < 0) | (halt >= 2 ** 32)).any():
-                raise ValueError("alt: one mask of capi.WHY_* per listed element")
-            halt = halt.astype(np.uint32)
-    shp = vet_shapes(L, n)
+    words = "32-bit integer tensor of idx's length"
+    # NOTHING SYNCHRONISES for device tensors (used where they lie, unread); host lists are checked here and uploaded once each below
+    here, lidx, n = _listed(mem, idx, "indices", "listed indices", "the region's planes", 0, P)
     wsb = vet.workspace(v, n)
-    if v.memory == capi.MEM_HOST:
-        arrays, ptr, stream = _host_arrays(shp, want, None), (lambda a: a.ctypes.data), None
-        lidx, lalt = hidx, halt
-        status = np.zeros(1, np.uint32)
-        ws = np.empty(max(wsb // 4, 1), np.int32)
-    else:
-        import torch          # (lazily: the package and its CPU route work without torch)
-        dev = torch.device("cuda", int(v.device))
-        if on_device:
-            for a, what, dts in ((idx, "idx", (torch.int32,)), (alt, "alt", (torch.int32, torch.uint32))):
-                if a is not None and (a.dtype not in dts or a.device != dev or a.dim() != 1 or not a.is_contiguous() or int(a.numel()) != n):
-                    raise ValueError("%s must be a contiguous one-dimensional 32-bit integer tensor of idx's length on %s" % (what, dev))
-            lidx, lalt = idx, alt
-        else:
-            lidx = torch.from_numpy(hidx).to(dev)
-            lalt = None if halt is None else torch.from_numpy(halt.view(np.int32)).to(dev)
-        tdt = {np.uint32: torch.uint32, np.int32: torch.int32, np.float32: torch.float32}
-        arrays = {k: torch.empty(shp[k][0], dtype=tdt[shp[k][1]], device=dev) for k in want}
-        ptr = lambda a: a.data_ptr()
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream().cuda_stream
-        status = torch.zeros(1, dtype=torch.int32, device=dev).view(torch.uint32)
-        ws = torch.empty(max(wsb // 4, 1), dtype=torch.int32, device=dev)
+    if here:
+        mem.check_list(lidx, "idx", words)
+        if alt is not None:
+            mem.check_list(alt, "alt", words, dtypes=(np.int32, np.uint32), n=n)
+    elif alt is not None:
+        alt = np.asarray(alt, np.int64).ravel()
+        if alt.size != n or ((alt < 0) | (alt >= 2 ** 32)).any():
+            raise ValueError("alt: one mask of capi.WHY_* per listed element")
+    arrays = _arrays(mem, vet_shapes(L, n), want)
+    ws, status = _scratch(mem, wsb), mem.zeros(1, np.uint32)
+    if not here:                                                  # host lists: one upload each
+        lidx = mem.upload(lidx.astype(np.int32))
+        alt = None if alt is None else mem.upload(alt.astype(np.uint32))
     if n:
-        vet.sites(v, d, params, ptr(lidx), None if lalt is None else ptr(lalt), n, n, status=ptr(status), workspace=ptr(ws), stream=stream,
-                  **{k: ptr(arrays[k]) for k in want})
+        vet.sites(v, d, params, mem.ptr(lidx), None if alt is None else mem.ptr(alt), n, n, status=mem.ptr(status), workspace=mem.ptr(ws), stream=mem.stream,
+                  **_ptrs(mem, arrays))
     del keepalive
-    res = {"pos0": pos0, "n": n, "n_lib": L, "status": status}
-    res.update(arrays)
-    return res
+    return dict({"pos0": pos0, "n": n, "n_lib": L, "status": status}, **arrays)

@@ -660,13 +660,12 @@ def test_hip_adopted_arenas_equal_copied_ones(dev_lib, oracle_lib, per_lib):
     got = eng.end_region()
     parity.assert_results_equal(got, want[0], "adopted arenas")
     assert eng.format_region("chrS") == want_text
-    w_ad = capi._region_warnings(eng, "chrS") if hasattr(capi, "_region_warnings") else None
+    w_ad = eng.region_warnings("chrS")
     # the same engine, next region, copied this time; then a region that tries both kinds
     eng.begin_region(0, 0, 5000, ref); eng.push_reads(arrs)
     got2 = eng.end_region()
     parity.assert_results_equal(got2, want[0], "copied arenas")
-    if w_ad is not None:
-        assert capi._region_warnings(eng, "chrS") == w_ad
+    assert eng.region_warnings("chrS") == w_ad
     if dev_lib.kind().startswith("hip"):
         eng.begin_region(0, 0, 5000, ref); eng.push_reads(capi.select_reads(arrs, np.arange(0, 10)))
         with pytest.raises(capi.BrcError):

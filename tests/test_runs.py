@@ -592,7 +592,7 @@ def test_tensors_runs_names_and_the_chain_into_bins(route, oracle_lib, low_regio
     eng.close()
     # names need an engine that keeps libraries apart
     eng = td.computed(route.engine_lib, arrs, 50, 2950, ref)
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="^libs names libraries: the engine reports one set of counts for all of them$"):
         tensors.runs(eng, route.runs, cuts=cuts, libs=[names[0]])
     eng.close()
 

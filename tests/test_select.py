@@ -902,6 +902,6 @@ def test_tensors_select_names_errors_and_the_chain_to_sites(route, oracle_lib, t
     eng.close()
     # names need an engine that keeps libraries apart
     eng = td.computed(route.engine_lib, arrs, 50, 2950, ref)
-    with pytest.raises(ValueError):
+    with pytest.raises(ValueError, match="^case / control name libraries: the engine reports one set of counts for all of them$"):
         tensors.select(eng, route.select, case=[names[0]], **kw)
     eng.close()

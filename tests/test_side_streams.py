@@ -29,10 +29,12 @@ panel 26 us, select 50 us, bins 49 us, runs 27 us, indels 53 us — twenty times
 host's queueing of the seven input copies, up to twenty fills and the call itself — at a pessimistic half millisecond each some 15 ms —
 so it never goes below 50 ms; it is capped at 0.25 s.  kernel_s of the six calls behind that hold: 13 to 33 us.
 
-Which bam_readcount_amd.tensors functions may wait for their stream (read off tensors.py):
+Which bam_readcount_amd.tensors functions may wait for their stream (read off tensors.py: the host reads device memory in one place,
+_Device.read, which only the count-then-fill helper _sized_by_data calls; host lists go up in one place, _Device.upload):
   region                      never: every size is known on the host                                     -> asserted
   bins(width=) and bins(edges= a device tensor)   never                                                 -> asserted for width=
-  bins(edges= a host list), sites(positions= / windows= on the host)   upload pageable host memory: the copy may wait
+  vet(idx=, alt= device tensors), sites(positions= a device tensor)   never: every size follows from the list's length -> asserted for vet
+  bins(edges= a host list), vet(idx= a host list), sites(positions= / windows= on the host)   upload pageable host memory: the copy may wait
   sites(indels=), indels, select, runs            SYNCHRONISE ONCE by contract: the host reads a count to size the arrays
 
 Not here: graph capture (not promised), the inflate and deflate libraries (a stream of their own), sanitizers, machine code."""
@@ -50,6 +52,7 @@ import test_indels as ti
 import test_panel as tp
 import test_runs as tr
 import test_select as ts
+import test_vet as tv
 
 P, POS0, L = 600, 1000, 2                 # three workgroups of 256 positions, two libraries
 K0, N = 5, 590                            # the window of the calls: off the 64-grid at both ends
@@ -69,18 +72,18 @@ HOLD_FLOOR, HOLD_CAP = 0.05, 0.25         # seconds
 
 
 class Route(tr.Route):
-    """test_runs.Route (engine + dense + select + runs) with the bins, panel and indels libraries of the same kind, and a second
+    """test_runs.Route (engine + dense + select + runs) with the bins, panel, indels and vet libraries of the same kind, and a second
     handle of the two libraries that take a workspace"""
 
     def __init__(self, name):
         tr.Route.__init__(self, name)
         if name == "hip":
-            self.bins, self.panel, self.indels = capi.Bins(), capi.Panel(), capi.Indels()
+            self.bins, self.panel, self.indels, self.vet = capi.Bins(), capi.Panel(), capi.Indels(), capi.Vet()
             self.select2, self.runs2 = capi.Select(), capi.Runs()
         else:
-            for m in (tb, tp, ti):
+            for m in (tb, tp, ti, tv):
                 subprocess.check_call(["make", "-s", "-C", m.SIM_DIR], stderr=subprocess.DEVNULL)
-            self.bins, self.panel, self.indels = capi.Bins(tb.SIM_LIB), capi.Panel(tp.SIM_LIB), capi.Indels(ti.SIM_LIB)
+            self.bins, self.panel, self.indels, self.vet = capi.Bins(tb.SIM_LIB), capi.Panel(tp.SIM_LIB), capi.Indels(ti.SIM_LIB), capi.Vet(tv.SIM_LIB)
             self.select2, self.runs2 = capi.Select(ts.SIM_LIB), capi.Runs(tr.SIM_LIB)
 
     def alloc(self, n_bytes):
@@ -565,6 +568,51 @@ def test_the_expected_bytes_are_what_the_cpu_builds_give(sim_route):
             compare(got, job.expect(world), "%s [%s]" % (name, state))
 
 
+NUMPY_ALONE = '''
+import sys
+sys.path.insert(0, %(root)r); sys.path.insert(0, %(root)r + "/tests")
+import numpy as np
+import synth
+from bam_readcount_amd import capi, tensors
+from test_dense import computed
+lib = %(libs)r
+ref = synth.make_ref(np.random.default_rng(11), 1000)
+arrs = synth.make_batch(77, ref, 50, read_len=(60, 120), style="indel", n_libs=2, mismatch=0.06)
+eng = computed(capi.Library(lib["engine"]), arrs, 20, 980, ref, lib_names=["libA", "libB"], per_lib=True)
+indels = capi.Indels(lib["indels"])
+got = {"region": tensors.region(eng, capi.Dense(lib["dense"]), want=tensors.KINDS), "indels": tensors.indels(eng, indels)}
+got["select"] = sel = tensors.select(eng, capi.Select(lib["select"]), case=["libA"], control=["libB"], min_depth=1, min_alt=1, ctl_max_frac=(1, 2))
+got["sites"] = tensors.sites(eng, capi.Panel(lib["panel"]), positions=sel["pos"], want=tensors.KINDS, indels=indels)
+got["windows"] = tensors.sites(eng, capi.Panel(lib["panel"]), windows=([100, 300], [110, 301]))
+got["runs"] = runs = tensors.runs(eng, capi.Runs(lib["runs"]), cuts=(1, 3), libs=["libB", 0], ref_n=True)
+got["bins"] = tensors.bins(eng, capi.Bins(lib["bins"]), width=64, thresholds=(1, 4), hist=8)
+got["edges"] = tensors.bins(eng, capi.Bins(lib["bins"]), edges=np.stack([runs["start"], runs["end"]], axis=1).reshape(-1))
+got["vet"] = tensors.vet(eng, capi.Vet(lib["vet"]), idx=sel["idx"], alt=sel["why"], libs=["libA"], min_depth=1, min_var_count=1)
+n = got["region"]["n"]
+assert 900 < n <= 961 and got["indels"]["m"] > 0 and sel["n"] > 0 and runs["n"] > 1 and got["windows"]["n"] == 11
+assert got["sites"]["n"] == got["vet"]["n"] == sel["n"] and got["bins"]["n_bins"] == (n + 63) // 64 and got["edges"]["n_bins"] == 2 * runs["n"] - 1
+for name, r in got.items():
+    for k, a in dict(r, **r.get("indels", {})).items():
+        assert isinstance(a, (int, dict, np.ndarray)), (name, k, type(a))
+assert not [m for m in sys.modules if m.split(".")[0] == "torch"], "the CPU route imported torch"
+print("NUMPY ALONE OK")
+'''
+
+
+def test_the_host_route_needs_numpy_alone(sim_route, tmp_path):
+    """tensors' promise that importing the package, and the CPU route, need numpy alone: in a process of its own every entry point of
+    bam_readcount_amd.tensors — region, indels, select, sites (a list, windows, indels=), runs, bins (width=, edges=) and vet — on a
+    small region computed by the CPU builds, and torch is in sys.modules neither before nor after"""
+    import sys
+    from conftest import ROOT
+    r = sim_route
+    libs = dict(engine=r.engine_lib.path, **{k: getattr(r, k).path for k in ("dense", "indels", "select", "panel", "runs", "bins", "vet")})
+    script = tmp_path / "numpy_alone.py"
+    script.write_text(NUMPY_ALONE % dict(root=ROOT, libs=libs))
+    p = subprocess.run([sys.executable, str(script)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0 and b"NUMPY ALONE OK" in p.stdout, p.stderr.decode()[-3000:]
+
+
 # ------------------------------------------------------------------------------------------------ the GPU: holds
 
 class Hold:
@@ -762,9 +810,10 @@ def low_region(oracle_lib):
 
 @pytest.mark.gpu
 def test_tensors_functions_under_a_held_stream(gpu, low_region):
-    """tensors.region / indels / sites / select / bins / runs on an engine-computed region inside `with torch.cuda.stream(s)`, behind a
-    hold, with a torch op of the caller's queued behind each: the results are the references.  region and bins(width=) must return
-    while the hold runs; the others read a count (or upload a host list) and may wait — see the module's text."""
+    """tensors.region / indels / sites / select / bins / runs / vet on an engine-computed region inside `with torch.cuda.stream(s)`,
+    behind a hold, with a torch op of the caller's queued behind each: the results are the references.  region, bins(width=) and vet
+    on device lists (a select result from outside the held window) must return while the hold runs; the others read a count (or
+    upload a host list) and may wait — see the module's text."""
     from bam_readcount_amd import tensors
     torch, route = gpu.torch, gpu.route
     ref, arrs, res = low_region
@@ -774,13 +823,18 @@ def test_tensors_functions_under_a_held_stream(gpu, low_region):
     p = ts.TWOLIB_PARAMS[2][1]
     pos = (p0 + np.array([0, 1, 63, 64, 65, 200, 200, 1000, P_ - 1])).tolist()
     cuts = (2, 5)
+    VD = tv.Dense.of(res)
+    vidx, vwhy = tv.select_list(VD, 1)
+    sel = tensors.select(eng, route.select, indel=False, min_depth=0, min_alt=1)          # vet's device lists: made outside the held window
+    assert sel["n"] == len(vidx) > 20 and sel["idx"].is_cuda and sel["why"].is_cuda
     calls = {"region": lambda: tensors.region(eng, route.dense, want=tensors.KINDS),
              "bins": lambda: tensors.bins(eng, route.bins, width=64, thresholds=(1, 4), hist=8),
              "indels": lambda: tensors.indels(eng, route.indels),
              "sites": lambda: tensors.sites(eng, route.panel, positions=pos, want=tensors.KINDS),
              "select": lambda: tensors.select(eng, route.select, role=[1, 2], min_depth=p["min_depth"], min_alt=p["min_alt"], min_frac=p["frac"], ctl_max_frac=p["ctl_frac"]),
-             "runs": lambda: tensors.runs(eng, route.runs, cuts=cuts, combine="max", ref_n=True)}
-    first = {"region": "depth", "bins": "sums", "indels": "pos", "sites": "depth", "select": "idx", "runs": "k0"}
+             "runs": lambda: tensors.runs(eng, route.runs, cuts=cuts, combine="max", ref_n=True),
+             "vet": lambda: tensors.vet(eng, route.vet, idx=sel["idx"], alt=sel["why"], **tv.EASY_LOW)}
+    first = {"region": "depth", "bins": "sums", "indels": "pos", "sites": "depth", "select": "idx", "runs": "k0", "vet": "keep"}
     for f in calls.values():                                             # (torch's own kernels of these paths, loaded outside the held window)
         f()
     torch.cuda.synchronize()
@@ -794,7 +848,7 @@ def test_tensors_functions_under_a_held_stream(gpu, low_region):
             got[name] = r = f()
             pending = not e.query()
             seen[name] = r[first[name]].view(torch.int32).clone()        # the caller's own op, queued behind the call
-        if name in ("region", "bins"):
+        if name in ("region", "bins", "vet"):
             assert pending, "INCONCLUSIVE or a wait: tensors.%s returned after the hold of %.1f ms on its stream had run out" % (name, 1e3 * gpu.hold.seconds)
         s.synchronize()
         assert np.array_equal(seen[name].cpu().numpy(), r[first[name]].view(torch.int32).cpu().numpy()), name
@@ -810,4 +864,5 @@ def test_tensors_functions_under_a_held_stream(gpu, low_region):
     tp.check_sites(route, got["sites"], res, pos, np.arange(len(pos)), "sites on a stream")
     ts.check_select(route, got["select"], dense, [1, 2], p, "select on a stream")
     tr.check_runs(route, got["runs"], dense, 0, P_, cuts, "runs on a stream", combine=tr.MAX, ref_n=True)
+    tv.check_vet(route, got["vet"], VD, vidx, vwhy, "vet on a stream", **tv.EASY_LOW)
     eng.close()

@@ -38,7 +38,7 @@ for it in range(int(sys.argv[3])):
             elif op == "format": eng.format_region("chrS")
             elif op == "clear": eng.clear_indel_queue()
             elif op == "counts": eng.counts()
-            elif op == "warn": capi._region_warnings(eng, "chrS") if hasattr(capi, "_region_warnings") else None
+            elif op == "warn": eng.region_warnings("chrS")
             elif op == "opt": lib.lib.brc_set_option(eng.h, random.randint(0, 9), random.choice([0, 1, 2, -1, 10**12]))
             elif op == "chrom": lib.lib.brc_set_chrom(eng.h, random.choice([b"chrS", b"", None]))
             elif op == "compute_n": eng.compute_n(random.choice([-1, 0, 1, 3, 40]))
@@ -47,7 +47,7 @@ for it in range(int(sys.argv[3])):
                 k = random.randint(0, 6); wb = np.array([random.randint(-50, 1600) for _ in range(k)], np.int32)
                 eng.region_windows(wb, wb + np.array([random.choice([0, 1, 2, 70, 400]) for _ in range(k)], np.int32))
             elif op == "bigpush": eng.push_reads(big)              # (above the staging pool's threshold)
-            elif op == "window": capi._format_window(eng, "chrS", random.randint(0, 500), random.randint(0, 900), random.randint(-5, 5))
+            elif op == "window": eng.format_window("chrS", random.randint(0, 500), random.randint(0, 900), random.randint(-5, 5))
         except capi.BrcError as e:
             k = str(e)[:60]; errs[k] = errs.get(k, 0) + 1
         except Exception as e:
