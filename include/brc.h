@@ -347,7 +347,8 @@ int  brc_device_view_get(brc_engine*, brc_device_view* out);   /* after brc_comp
  *   offsets rebased to the region), NOT the engine's event-byte stream: that stream is an engine internal whose encoding (escape
  *   bytes, a sparse wide stream) is no ABI, while seq4 is SAMv1's.
  *       seq4, seq_off [n_reads], l_qseq [n_reads]   inserted base j of a record: nibble rep_qpos + 1 + j of read rep_read (high nibble
- *             first) through "=ACGTN" (A C G T N '=' themselves, every other code N); N when that offset is at or past l_qseq
+ *             first) through "=ACGTN" (A C G T N '=' themselves, every other code N); N when that offset is at or past l_qseq or
+ *             below 0, and when rep_read is not below n_reads
  *       ref, ref_lo, ref_hi, ref_len   ref[p - ref_lo] is the raw reference character of contig position p for ref_lo <= p < ref_hi
  *             (the slice the engine uploaded: it covers every pushed read); deleted base j of a record is position pos + 1 + j, N where
  *             the slice has none (p >= ref_len, outside the slice, a NUL character, ref == NULL).
