@@ -1058,3 +1058,74 @@ class Vet(_Handle):
     def last_timing(self):
         """kernel seconds (waits for the launches of the last call), bytes asked for and written"""
         return super().last_timing()
+
+
+# ---------------------------------------------------------------- device-side indel candidate filter (include/brc_ivet.h)
+IVET_LIB = os.path.join(HERE, "csrc", "libbrc_ivet_hip.so")
+IVET_EXPORTS = [
+    "brc_ivet_create", "brc_ivet_destroy", "brc_ivet_kind", "brc_ivet_last_error", "brc_ivet_workspace", "brc_ivet_records", "brc_ivet_last_timing",
+]
+IVET_MAX_LIB, IVET_NVAL = 254, 20
+IVET_TESTS = tuple(t for t in VET_TESTS if t != "VAR_BQ") + ("CTL_DEPTH", "CTL_ALLELE")
+IVET_BIT = dict({t: VET_BIT[t] for t in VET_TESTS if t != "VAR_BQ"}, CTL_DEPTH=1 << 18, CTL_ALLELE=1 << 19)      # the shared tests keep brc_vet.h's bits
+IVET_ALL_TESTS = sum(IVET_BIT.values())
+IVET_NOT_ASKED, IVET_NO_SITE = VET_NOT_ASKED, VET_NO_SITE
+IVET_LIST_OUT_OF_RANGE, IVET_LIST_NOT_ASCENDING, IVET_TABLE_OUT_OF_RANGE, IVET_TABLE_NOT_ASCENDING = 1, 2, 4, 8
+IVET_UINTS = VET_UINTS + ("ctl_min_depth", "ctl_max_count", "ctl_frac_num", "ctl_frac_den")
+IVET_FLOATS = tuple(k for k in VET_FLOATS if k != "min_var_bq")
+IVET_DEFAULTS = dict({k: x for k, x in VET_DEFAULTS.items() if k != "min_var_bq"}, ctl_min_depth=0, ctl_max_count=0, ctl_frac_num=1, ctl_frac_den=1)
+
+
+class IVetParams(C.Structure):
+    """brc_ivet_params (include/brc_ivet.h)"""
+    _fields_ = [("role", C.c_void_p), ("tests", C.c_uint32), ("kinds", C.c_uint32)] + [(k, C.c_uint32) for k in IVET_UINTS] + [(k, C.c_float) for k in IVET_FLOATS]
+
+
+class IVetTable(C.Structure):
+    """brc_ivet_table (include/brc_ivet.h): the table brc_indels_gather writes, where it lies"""
+    _fields_ = [("m", C.c_int64), ("stride", C.c_int64), ("pos", C.c_void_p), ("lib", C.c_void_p), ("len", C.c_void_p), ("istat", C.c_void_p),
+                ("fstat", C.c_void_p), ("allele_off", C.c_void_p), ("alleles", C.c_void_p), ("alleles_len", C.c_int64)]
+
+
+def ivet_params(role=None, tests=IVET_ALL_TESTS, kinds=WHY_INS | WHY_DEL, **thresholds):
+    """(IVetParams, keepalive): role is a sequence of ROLE_* per library or None (every library a case library), tests a mask of IVET_BIT
+    values, kinds a mask of WHY_INS | WHY_DEL; thresholds are the members of brc_ivet_params by name, IVET_DEFAULTS where not given"""
+    unknown = set(thresholds) - set(IVET_DEFAULTS)
+    if unknown:
+        raise TypeError("unknown thresholds %r" % sorted(unknown))
+    t = dict(IVET_DEFAULTS, **thresholds)
+    p = IVetParams(None, tests, kinds, *[t[k] for k in IVET_UINTS + IVET_FLOATS])
+    keepalive = None
+    if role is not None:
+        keepalive = np.ascontiguousarray(role, np.uint8)
+        p.role = keepalive.ctypes.data
+    return p, keepalive
+
+
+class IVet(_Handle):
+    """One handle of a library exporting include/brc_ivet.h: the product's libbrc_ivet_hip.so (default; raises when it is not built or
+    there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_ivet).  records() takes raw
+    addresses; bam_readcount_amd.tensors.vet_indels() is the interface that allocates and returns arrays."""
+
+    PREFIX, EXPORTS, LIB, NAME = "brc_ivet", IVET_EXPORTS, IVET_LIB, "ivet"
+    PROTOS = {"brc_ivet_workspace": (C.c_int64, [C.POINTER(DeviceView), C.c_int64]),
+              "brc_ivet_records": (C.c_int, [C.c_void_p, C.POINTER(DeviceView), C.POINTER(DeviceIndels), C.POINTER(IVetParams), C.POINTER(IVetTable),
+                                             C.c_void_p, C.c_void_p, C.c_int64, C.c_int64] + [C.c_void_p] * 7)}
+
+    def workspace(self, view, m):
+        """bytes of scratch a call over a table of m records needs"""
+        return int(self.lib.brc_ivet_workspace(_ref(view), m))
+
+    def records_raw(self, view, indels, params, table, idx, why, n, dst_stride, fail=None, vals=None, ctl_count=None, keep=None, status=None,
+                    workspace=None, stream=None):
+        """brc_ivet_records as it is: table arrays, lists, scratch, destinations and the status word are addresses (or None) in memory of
+        the views' kind; returns the code."""
+        return self.lib.brc_ivet_records(self.h, _ref(view), _ref(indels), _ref(params), _ref(table), idx, why, n, dst_stride, fail, vals, ctl_count, keep,
+                                         status, workspace, stream)
+
+    def records(self, view, indels, params, table, idx, why, n, dst_stride, **kw):
+        self._check("brc_ivet_records", self.records_raw(view, indels, params, table, idx, why, n, dst_stride, **kw))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last call), bytes asked for and written"""
+        return super().last_timing()

@@ -40,6 +40,13 @@ bucket against reference bucket of the same site.  vet() runs them on a list whe
 synchronisation: select -> vet -> sites is a chain of device lists:
     r = tensors.vet(eng, capi.Vet(), idx=sel["idx"], alt=sel["why"], min_var_count=4, min_var_mapq=20.0)
     panel = tensors.sites(eng, capi.Panel(), positions=sel["pos"][r["keep"].nonzero()[:, 0]])
+
+Indel candidates are judged on the records of the indel table: vet_indels() runs the same tests on every record — its own sums against
+the reference base's bucket at its position — and an allele-aware control veto (a control library's record of the same position,
+length and text), by libbrc_ivet_hip.so (capi.IVet), with no synchronisation.  select()'s own control veto does not compare allele
+text, so it runs with the control libraries ignored:
+    sel = tensors.select(eng, select, role=[1, 0], snv=False, min_depth=8, min_alt=3)
+    r = tensors.vet_indels(eng, capi.IVet(), tensors.indels(eng, capi.Indels()), idx=sel["idx"], why=sel["why"], role=[1, 2])
 """
 from functools import lru_cache, partial
 
@@ -258,7 +265,7 @@ def _library_names(engine, n_lib, who):
     return names
 
 
-# ------------------------------------------------------------------------------------------------ the seven entry points
+# ------------------------------------------------------------------------------------------------ the eight entry points
 
 KINDS = ("istat", "fstat", "metrics", "depth", "ncol", "unavail")
 DEFAULT_WANT = ("istat", "fstat", "metrics", "depth", "ncol")
@@ -760,3 +767,143 @@ def vet(engine, vet, *, idx, alt=None, libs=None, tests=None, want=VET_KINDS, **
                   **_ptrs(mem, arrays))
     del keepalive
     return dict({"pos0": pos0, "n": n, "n_lib": L, "status": status}, **arrays)
+
+
+IVET_KINDS = ("fail", "keep", "vals", "ctl_count")
+_IVET_KIND_BITS = {"ins": capi.WHY_INS, "del": capi.WHY_DEL}
+
+
+def ivet_shapes(m, n):
+    """kind -> (shape, numpy dtype) of vet_indels()'s arrays for a table of m records and a list of n elements"""
+    return {"fail": ((m,), np.uint32), "keep": ((n,), np.int32), "vals": ((capi.IVET_NVAL, m), np.float32), "ctl_count": ((m,), np.uint32)}
+
+
+def _ivet_tests(tests):
+    if tests is None:
+        return capi.IVET_ALL_TESTS
+    if isinstance(tests, (int, np.integer)) and not isinstance(tests, bool):
+        if int(tests) < 0 or int(tests) & ~capi.IVET_ALL_TESTS:
+            raise ValueError("tests: a mask of capi.IVET_BIT values (VAR_BQ is not a test of indel records)")
+        return int(tests)
+    mask = 0
+    for t in ([tests] if isinstance(tests, str) else list(tests)):
+        if t not in capi.IVET_BIT:
+            raise ValueError("unknown test %r (one of %r)" % (t, capi.IVET_TESTS))
+        mask |= capi.IVET_BIT[t]
+    return mask
+
+
+def vet_indels(engine, ivet, table, *, idx=None, why=None, role=None, case=None, control=None, kinds=("ins", "del"), tests=None, want=IVET_KINDS,
+               **thresholds):
+    """The read-metric tests of include/brc_ivet.h on every record of a sorted indel TABLE of the engine's last computed region — the
+    record's own sums against the reference base's bucket at the record's pileup position, the seventeen tests of vet() other than
+    VAR_BQ — and an ALLELE-AWARE control veto: CTL_ALLELE is set when a control library has a record of the same position, length and
+    text whose count fails count <= ctl_max_count and count / depth <= ctl_frac_num / ctl_frac_den; CTL_DEPTH when a control library
+    is shallower than ctl_min_depth there.
+
+    table: the dict indels(...) returns, or sites(..., indels=...)["indels"]: pos, lib, len, istat, fstat, allele_off, alleles and "m",
+         used where they lie (an array that is not contiguous is packed first: a copy on the stream, no wait).
+    idx, why: optionally select()'s list ("idx", "why"), non-decreasing plane indices — a sequence or numpy array, or (HIP libraries)
+         int32 torch tensors on the engine's device, used where they lie.  why None: insertions and deletions both count.
+    role / case / control: as in select(); none of them: every library is a case library (no control test can fail).
+    kinds: the kinds of record judged, of "ins" and "del".
+    tests: names of capi.IVET_TESTS, or a mask of capi.IVET_BIT values (None: all nineteen).
+    thresholds: members of brc_ivet_params by name; capi.IVET_DEFAULTS where not given: vet()'s defaults, ctl_min_depth 0,
+         ctl_max_count 0 and ctl_frac 1 / 1 — any read of the same allele in a control library vetoes.
+
+    Returns every kind in `want` — "fail": uint32 [m] failure words (capi.IVET_BIT; capi.IVET_NOT_ASKED, capi.IVET_NO_SITE: nothing
+    judged), "vals": float32 [capi.IVET_NVAL, m] the numbers compared (capi.VET_V_NAMES), "ctl_count": uint32 [m] the largest count of
+    a control record of the same allele, "keep": int32 [n] per list element the OR of capi.WHY_INS / WHY_DEL over its records that
+    pass every test (restricted to the kinds in why) — plus "status" (one uint32 element in the arrays' memory: capi.IVET_LIST_* /
+    IVET_TABLE_* bits, written by the kernels, not read by this call) and the ints "m", "n", "n_lib", "pos0".
+    With the HIP libraries the arrays are torch tensors on the engine's device, filled on torch's current stream; with the CPU builds
+    they are numpy arrays.  NOTHING SYNCHRONISES: every size follows from table["m"] and n.
+
+    An allele-aware veto end to end: select()'s own control veto does not compare allele text, so run it with the control libraries
+    IGNORED, and give them to vet_indels as control:
+        sel = select(eng, s, role=[1, 0], snv=False, min_depth=8, min_alt=3)           # library 1 (the normal) ignored
+        t = indels(eng, capi.Indels())
+        r = vet_indels(eng, capi.IVet(), t, idx=sel["idx"], why=sel["why"], role=[1, 2], ctl_max_count=1)
+        panel = sites(eng, capi.Panel(), positions=sel["pos"][r["keep"].nonzero()[:, 0]])
+    ValueError for what the library would refuse, before anything is queued."""
+    want = _check_want(want, IVET_KINDS)
+    mask = _ivet_tests(tests)
+    kmask = 0
+    for x in ([kinds] if isinstance(kinds, str) else list(kinds)):
+        if x not in _IVET_KIND_BITS:
+            raise ValueError("kinds: of 'ins' and 'del'")
+        kmask |= _IVET_KIND_BITS[x]
+    if not kmask:
+        raise ValueError("kinds: at least one of 'ins' and 'del'")
+    unknown = set(thresholds) - set(capi.IVET_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown thresholds %r (capi.IVET_DEFAULTS has the names)" % sorted(unknown))
+    t = dict(capi.IVET_DEFAULTS, **thresholds)
+    for k in capi.IVET_UINTS:
+        t[k] = _u32(t[k], k)
+    if t["freq_den"] == 0 or t["strand_den"] == 0 or t["ctl_frac_den"] == 0:
+        raise ValueError("a fraction's denominator must not be 0")
+    for k in capi.IVET_FLOATS:
+        with np.errstate(over="ignore"):
+            x = np.float32(t[k])
+        if isinstance(t[k], bool) or not np.isfinite(x):
+            raise ValueError("%s must be a finite number (in fp32)" % k)
+        t[k] = float(x)
+    v, d = engine.device_view(), engine.device_indels()
+    P, pos0, L = int(v.n_pos), int(v.pos0), int(v.n_lib)
+    if L > capi.IVET_MAX_LIB:
+        raise ValueError("the filter takes at most %d libraries" % capi.IVET_MAX_LIB)
+    mem = _memory(v)
+    params, keepalive = capi.ivet_params(_roles(engine, L, role, case, control), mask, kmask, **t)
+    # the table, where it lies
+    need = ("pos", "lib", "len", "istat", "fstat") + (("allele_off", "alleles") if mask & capi.IVET_BIT["CTL_ALLELE"] else ())
+    if not isinstance(table, dict) or "m" not in table or any(k not in table for k in need):
+        raise ValueError("table: the dict indels() returns, with %r" % (need,))
+    m = int(table["m"])
+    tab = capi.IVetTable(m, m)
+    held, shp = [], indel_shapes(m, 0)
+    for k in ("pos", "lib", "len", "istat", "fstat", "allele_off", "alleles"):
+        a = table.get(k)
+        if a is None:
+            continue
+        shape, dt = shp[k]
+        if _is_torch(a) != (mem.torch is not None) or tuple(a.shape) != (shape if k != "alleles" else tuple(a.shape)[:1]):
+            raise ValueError("table[%r] is not an array of shape %r of a table of %d records in the engine's memory" % (k, shape, m))
+        dts = (dt, np.int32) if dt == np.uint32 else (dt,)            # (torch code often carries unsigned words as int32)
+        if (a.dtype not in dts) if mem.torch is None else (a.dtype not in [mem.dtype[x] for x in dts]):
+            raise ValueError("table[%r] must hold %s" % (k, np.dtype(dt).name))
+        if mem.torch is not None and a.device != mem.dev:
+            raise ValueError("table[%r] must be a tensor on %s" % (k, mem.dev))
+        a = np.ascontiguousarray(a) if mem.torch is None else a.contiguous()      # (used where it lies; a strided selection is packed first)
+        held.append(a)
+        setattr(tab, k, mem.ptr(a))
+    if table.get("alleles") is not None:
+        tab.alleles_len = int(table["alleles"].shape[0])
+    if why is not None and idx is None:
+        raise ValueError("why needs idx")
+    n, lidx, here = 0, None, False
+    if idx is not None:
+        if why is not None and _is_torch(why) != _is_torch(idx):
+            raise ValueError("idx and why must be of one kind: both torch tensors or both host arrays")
+        words = "32-bit integer tensor of idx's length"
+        # NOTHING SYNCHRONISES for device tensors (used where they lie, unread); host lists are checked here and uploaded once each below
+        here, lidx, n = _listed(mem, idx, "indices", "listed indices", "the region's planes", 0, P)
+        if here:
+            mem.check_list(lidx, "idx", words)
+            if why is not None:
+                mem.check_list(why, "why", words, dtypes=(np.int32, np.uint32), n=n)
+        elif why is not None:
+            why = np.asarray(why, np.int64).ravel()
+            if why.size != n or ((why < 0) | (why >= 2 ** 32)).any():
+                raise ValueError("why: one mask of capi.WHY_* per listed element")
+    wsb = ivet.workspace(v, m)
+    arrays = _arrays(mem, ivet_shapes(m, n), want)
+    ws, status = _scratch(mem, wsb), mem.zeros(1, np.uint32)
+    if idx is not None and not here:                              # host lists: one upload each
+        lidx = mem.upload(lidx.astype(np.int32))
+        why = None if why is None else mem.upload(why.astype(np.uint32))
+    if m or n:
+        ivet.records(v, d, params, tab, mem.ptr(lidx) if n else None, mem.ptr(why) if (n and why is not None) else None, n, m, status=mem.ptr(status),
+                     workspace=mem.ptr(ws), stream=mem.stream, **_ptrs(mem, arrays))
+    del keepalive, held
+    return dict({"pos0": pos0, "m": m, "n": n, "n_lib": L, "status": status}, **arrays)
