@@ -5,8 +5,9 @@
     tensors   results of a computed region as arrays where the engine left them: torch tensors on the GPU, filled by the gfx950
               kernels of libbrc_dense_hip.so without a copy through the host (tensors.region); the side libraries beside it, each a
               library and a function of its own: indels, sites (panel), select, bins, runs, vet (the per-allele read-metric
-              tests on listed candidates, libbrc_vet_hip.so) and vet_indels (the same tests and an allele-aware control veto on
-              the records of the indel table, libbrc_ivet_hip.so)
+              tests on listed candidates, libbrc_vet_hip.so), vet_indels (the same tests and an allele-aware control veto on
+              the records of the indel table, libbrc_ivet_hip.so) and normalize_indels (the indel table left-aligned against
+              the reference and its equal records merged, libbrc_inorm_hip.so)
     shard     splitting a run over ranks / GPUs
 
 Submodules are imported on first use (`from bam_readcount_amd import tensors`); importing the package loads no native library and

@@ -1129,3 +1129,58 @@ class IVet(_Handle):
     def last_timing(self):
         """kernel seconds (waits for the launches of the last call), bytes asked for and written"""
         return super().last_timing()
+
+
+# ---------------------------------------------------------------- device-side indel normalisation (include/brc_inorm.h)
+INORM_LIB = os.path.join(HERE, "csrc", "libbrc_inorm_hip.so")
+INORM_EXPORTS = [
+    "brc_inorm_create", "brc_inorm_destroy", "brc_inorm_kind", "brc_inorm_last_error", "brc_inorm_workspace", "brc_inorm_table", "brc_inorm_last_timing",
+]
+INORM_MAX_SHIFT = 1 << 20
+INORM_NOT_JUDGED, INORM_LIMIT, INORM_EDGE = 1, 2, 4                 # bits of a record's flags
+INORM_TABLE_BAD, INORM_ANY_LIMIT, INORM_ANY_EDGE = 1, 2, 4          # bits of the status word
+INORM_SRC_DESTS = ("npos", "shift", "flags", "group")
+INORM_DESTS = ("pos", "lib", "len", "rep_read", "rep_qpos", "members", "istat", "fstat", "metrics", "allele_off", "alleles")
+
+
+class INormParams(C.Structure):
+    """brc_inorm_params (include/brc_inorm.h)"""
+    _fields_ = [("max_shift", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class INormSource(C.Structure):
+    """brc_inorm_source (include/brc_inorm.h): the input table, where it lies"""
+    _fields_ = [("m", C.c_int64), ("stride", C.c_int64), ("pos", C.c_void_p), ("lib", C.c_void_p), ("len", C.c_void_p), ("rep_read", C.c_void_p),
+                ("rep_qpos", C.c_void_p), ("istat", C.c_void_p), ("fstat", C.c_void_p), ("allele_off", C.c_void_p), ("alleles", C.c_void_p),
+                ("alleles_len", C.c_int64)]
+
+
+class INorm(_Handle):
+    """One handle of a library exporting include/brc_inorm.h: the product's libbrc_inorm_hip.so (default; raises when it is not built or
+    there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_inorm).  table() takes raw
+    addresses; bam_readcount_amd.tensors.normalize_indels() is the interface that allocates and returns arrays."""
+
+    PREFIX, EXPORTS, LIB, NAME = "brc_inorm", INORM_EXPORTS, INORM_LIB, "inorm"
+    PROTOS = {"brc_inorm_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+              "brc_inorm_table": (C.c_int, [C.c_void_p, C.POINTER(DeviceIndels), C.POINTER(INormParams), C.POINTER(INormSource), C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 + [C.c_int64, C.c_int64] + [C.c_void_p] * 13)}
+
+    def workspace(self, n, m):
+        """bytes of scratch a call over a window of n positions and a table of m records needs"""
+        return int(self.lib.brc_inorm_workspace(n, m))
+
+    def table_raw(self, indels, params, source, k0, n, workspace=None, workspace_bytes=0, counts=None, npos=None, shift=None, flags=None, group=None,
+                  cap=0, alleles_cap=0, pos=None, lib=None, len=None, rep_read=None, rep_qpos=None, members=None, istat=None, fstat=None, metrics=None,
+                  allele_off=None, alleles=None, status=None, stream=None):
+        """brc_inorm_table as it is: table arrays, scratch, destinations and the status word are addresses (or None) in memory of the
+        view's kind; returns the code."""
+        return self.lib.brc_inorm_table(self.h, _ref(indels), _ref(params), _ref(source), k0, n, workspace, workspace_bytes, counts, npos, shift, flags,
+                                        group, cap, alleles_cap, pos, lib, len, rep_read, rep_qpos, members, istat, fstat, metrics, allele_off, alleles,
+                                        status, stream)
+
+    def table(self, indels, params, source, k0, n, **kw):
+        self._check("brc_inorm_table", self.table_raw(indels, params, source, k0, n, **kw))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last call), bytes asked for and written"""
+        return super().last_timing()

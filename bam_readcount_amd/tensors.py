@@ -47,6 +47,8 @@ length and text), by libbrc_ivet_hip.so (capi.IVet), with no synchronisation.  s
 text, so it runs with the control libraries ignored:
     sel = tensors.select(eng, select, role=[1, 0], snv=False, min_depth=8, min_alt=3)
     r = tensors.vet_indels(eng, capi.IVet(), tensors.indels(eng, capi.Indels()), idx=sel["idx"], why=sel["why"], role=[1, 2])
+An aligner may place one indel anywhere inside a repeat: normalize_indels() left-aligns the table and merges what became equal first:
+    norm = tensors.normalize_indels(eng, capi.INorm(), tensors.indels(eng, lib)); r = tensors.vet_indels(eng, ivet, norm, role=[1, 2])
 """
 from functools import lru_cache, partial
 
@@ -825,6 +827,8 @@ def vet_indels(engine, ivet, table, *, idx=None, why=None, role=None, case=None,
         t = indels(eng, capi.Indels())
         r = vet_indels(eng, capi.IVet(), t, idx=sel["idx"], why=sel["why"], role=[1, 2], ctl_max_count=1)
         panel = sites(eng, capi.Panel(), positions=sel["pos"][r["keep"].nonzero()[:, 0]])
+    Records of one event placed apart inside a repeat meet only in a normalised table: vet_indels(eng, ivet, normalize_indels(eng, inorm,
+    indels(eng, lib)), role=[1, 2]); the verdicts go back to the raw records as r["fail"][norm["src"]["group"]] (group -1: not judged).
     ValueError for what the library would refuse, before anything is queued."""
     want = _check_want(want, IVET_KINDS)
     mask = _ivet_tests(tests)
@@ -907,3 +911,91 @@ def vet_indels(engine, ivet, table, *, idx=None, why=None, role=None, case=None,
                      workspace=mem.ptr(ws), stream=mem.stream, **_ptrs(mem, arrays))
     del keepalive, held
     return dict({"pos0": pos0, "m": m, "n": n, "n_lib": L, "status": status}, **arrays)
+
+
+INORM_KINDS = INDEL_KINDS + ("members",)
+_INORM_NEED = ("pos", "lib", "len", "istat", "fstat", "allele_off", "alleles")
+
+
+def _table_arrays(mem, table, need, optional):
+    """The arrays of an indel table dict, where they lie, validated as vet_indels() validates its table -> (m, {name: contiguous array});
+    a strided selection is packed first: a copy on the stream, no wait."""
+    if not isinstance(table, dict) or any(k not in table for k in ("m", "first", "n") + need):
+        raise ValueError("table: the dict indels() returns, with %r and its window 'm', 'first', 'n'" % (need,))
+    m = int(table["m"])
+    held, shp = {}, indel_shapes(m, 0)
+    for k in need + optional:
+        a = table.get(k)
+        if a is None:
+            continue
+        shape, dt = shp[k]
+        if _is_torch(a) != (mem.torch is not None) or tuple(a.shape) != (shape if k != "alleles" else tuple(a.shape)[:1]):
+            raise ValueError("table[%r] is not an array of shape %r of a table of %d records in the engine's memory" % (k, shape, m))
+        dts = (dt, np.int32) if dt == np.uint32 else (dt,)            # (torch code often carries unsigned words as int32)
+        if (a.dtype not in dts) if mem.torch is None else (a.dtype not in [mem.dtype[x] for x in dts]):
+            raise ValueError("table[%r] must hold %s" % (k, np.dtype(dt).name))
+        if mem.torch is not None and a.device != mem.dev:
+            raise ValueError("table[%r] must be a tensor on %s" % (k, mem.dev))
+        held[k] = np.ascontiguousarray(a) if mem.torch is None else a.contiguous()
+    return m, held
+
+
+def normalize_indels(engine, inorm, table, *, max_shift=1024, want=INORM_KINDS):
+    """A sorted indel TABLE of the engine's last computed region LEFT-ALIGNED against the uploaded reference and MERGED — include/
+    brc_inorm.h has the exact rule: every record steps left while the reference character at its position matches the last character
+    of its text (an insertion's text rotates, a deletion's becomes the reference's raw characters of the stretch it now deletes), at
+    most max_shift steps and not past the table's window or the reference slice; records that became equal in (position, library,
+    length, text) become one, with integer sums, fp32 sums in ascending input order and the thirteen columns of the sums.
+
+    table: the dict indels(...) returns, or sites(..., indels=...)["indels"]: pos, lib, len, istat, fstat, allele_off, alleles (rep_read
+         and rep_qpos where it has them) and "m", "first", "n" — the window is the table's own; used where they lie (an array that is
+         not contiguous is packed first: a copy on the stream, no wait).
+    max_shift: 0 .. capi.INORM_MAX_SHIFT; 0 merges without shifting.
+
+    Returns a dict of indels()'s shape — every kind in `want` (INORM_KINDS: INDEL_KINDS and "members": uint32 [m'], the records merged
+    into each) for the m' merged records, in indels()'s order, plus the ints "m" (= m'), "first", "n" — that vet_indels() takes as it
+    is, plus "src": {"npos": int32, "shift": uint32, "flags": uint32 (capi.INORM_NOT_JUDGED / INORM_LIMIT / INORM_EDGE), "group": int32}
+    [table["m"]] over the INPUT records — group is the merged record each went into, -1 for a record that is not judged — and
+    "status" (one uint32 element in the arrays' memory: capi.INORM_TABLE_BAD / INORM_ANY_LIMIT / INORM_ANY_EDGE, written by the
+    kernels, not read by this call).  rep_read and rep_qpos are those of a class's first member: provenance only.
+    With the HIP libraries the arrays are torch tensors on the engine's device, filled on torch's current stream, the scratch comes
+    from torch.empty; with the CPU builds they are numpy arrays.
+
+    SYNCHRONISES ONCE: the merged table's sizes are data.  A first call asks for the two counts alone, the host reads them (as
+    torch.nonzero does), then the arrays are allocated exactly and a second call fills them without another wait.
+    ValueError for what the library would refuse, before anything is queued."""
+    want = _check_want(want, INORM_KINDS)
+    if isinstance(max_shift, bool) or int(max_shift) != max_shift or not 0 <= int(max_shift) <= capi.INORM_MAX_SHIFT:
+        raise ValueError("max_shift: an integer in [0, %d]" % capi.INORM_MAX_SHIFT)
+    d = engine.device_indels()
+    pos0, P = int(d.pos0), int(d.n_pos)
+    mem = _memory(d, "brc_device_indels")
+    m, held = _table_arrays(mem, table, _INORM_NEED, ("rep_read", "rep_qpos"))
+    first, n = int(table["first"]), int(table["n"])
+    k0 = first - pos0 if n else 0
+    if n < 0 or k0 < 0 or k0 + n > P:
+        raise ValueError("table: its window [%d, %d) lies outside the region's positions [%d, %d)" % (first, first + n, pos0, pos0 + P))
+    src = capi.INormSource(m, m, alleles_len=int(held["alleles"].shape[0]))
+    for k, a in held.items():
+        setattr(src, k, mem.ptr(a))
+    params = capi.INormParams(int(max_shift))
+    wsb = inorm.workspace(n, m)
+    ws, status = _scratch(mem, wsb), mem.zeros(1, np.uint32)
+    if m and not n:                                               # (a window of no positions: the library judges nothing and writes nothing)
+        per = {"npos": held["pos"] + 0, "shift": mem.zeros((m,), np.uint32), "flags": mem.zeros((m,), np.uint32), "group": mem.zeros((m,), np.int32) - 1}
+    else:
+        per = {"npos": mem.empty((m,), np.int32), "shift": mem.empty((m,), np.uint32), "flags": mem.empty((m,), np.uint32), "group": mem.empty((m,), np.int32)}
+
+    def shapes_of(mm, nbytes):
+        return dict(indel_shapes(mm, nbytes), members=((mm,), np.uint32))
+
+    def call(**kw):                                               # (the per-record arrays and the status word ride on the filling call)
+        if "counts" not in kw:
+            kw = dict(kw, status=mem.ptr(status), **_ptrs(mem, per))
+        inorm.table(d, params, src, k0, n, workspace=mem.ptr(ws), workspace_bytes=wsb, stream=mem.stream, **kw)
+    # ONE WAIT: the two sizes are data
+    (mm, nbytes), arrays = _sized_by_data(mem, call, 2, shapes_of, want, ("cap", "alleles_cap"), fill_empty=True)
+    if not want:                                                  # (nothing of the merged table wanted: the per-record arrays alone)
+        call(cap=0, alleles_cap=0)
+    del held
+    return dict({"m": mm, "first": first, "n": n, "src": per, "status": status}, **arrays)
