@@ -2,7 +2,9 @@
 // as libbrc_sim.so is the engine's.  The launches of the gfx950 library run here as loops on host memory: views with memory ==
 // BRC_MEM_HOST (what libbrc_sim.so hands out), scratch and destinations in host memory.  The record, slot and position loops run from the
 // LAST lane to the first: nothing may depend on the order of the lanes (a position's list of records comes out reversed against an
-// ascending run).  The compaction is a serial loop.  Test infrastructure only.
+// ascending run); with BRC_SIM_LANES=forward in the environment the record loop runs from the first record to the last, so that a test
+// can show a result under both orders.  The compaction is a serial loop.  Test infrastructure only.
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../bam_readcount_amd/csrc/brc_select_core.h"
@@ -35,7 +37,9 @@ int brc_select_sites(brc_select* h, const brc_device_view* v, const brc_device_i
     brcside::start(h);
     if (walks_records(J)) {
         memset(J.head, 0xff, (size_t)n * sizeof(uint32_t));
-        for (uint64_t r = J.n_xagg; r-- > 0;) link_lane(J, r);
+        const char* order = getenv("BRC_SIM_LANES");
+        if (order && !strcmp(order, "forward")) { for (uint64_t r = 0; r < J.n_xagg; ++r) link_lane(J, r); }
+        else for (uint64_t r = J.n_xagg; r-- > 0;) link_lane(J, r);
     }
     if (walks_slots(J)) {
         memset(J.flag, 0, (size_t)n * sizeof(uint32_t));

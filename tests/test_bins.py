@@ -143,7 +143,7 @@ def call(route, v, d, k0, n, width=0, edges=None, thr=(), n_hist=0, ds=None, wan
     nb = count_bins(n, width, edges)
     ds = nb + PAD if ds is None else ds
     nt, nh, dd = min(len(thr), 8), min(max(n_hist, 0), 4096), max(ds, 0)
-    bs, bc, bh, bt = route.sentinel(max(2 * L * NSUM * dd, 2)), route.sentinel(max(2 * L * nt * dd, 2)), route.sentinel(max(2 * L * nh, 2)), route.sentinel(1)
+    bs, bc, bh, bt = route.sentinel(max(2 * (L + 1) * NSUM * dd, 2)), route.sentinel(max(2 * L * nt * dd, 2)), route.sentinel(max(2 * L * nh, 2)), route.sentinel(1)
     be = route.put(np.asarray(edges, np.int32)) if edges is not None else None
     par = capi.bins_params(width, route.ptr(be) if be is not None else None, nb if edges is not None else 0, list(thr), n_hist)
     for k, x in (fields or {}).items():
@@ -152,6 +152,7 @@ def call(route, v, d, k0, n, width=0, edges=None, thr=(), n_hist=0, ds=None, wan
                                         C.byref(par) if params else None, k0, n, route.ptr(bs) if "sums" in want else None,
                                         route.ptr(bc) if "covered" in want else None, route.ptr(bh) if "hist" in want else None, ds,
                                         route.ptr(bt) if "status" in want else None, None)
+    assert (route.quads(bs)[L * NSUM * dd:] == SENT64).all(), "sums of a library behind the last one were written"      # (room for one library more)
     return (rc, int(route.words(bt)[0]), route.quads(bs)[:L * NSUM * dd].reshape(L, NSUM, dd).copy(), route.quads(bc)[:L * nt * dd].reshape(L, nt, dd).copy(),
             route.quads(bh)[:L * nh].reshape(L, nh).copy())
 
@@ -353,6 +354,82 @@ def test_254_libraries(route):
     assert v.n_lib == 254 and v.n_xagg > 0
     check(route, v, d, D, width=7, what="254 libraries, width 7")
     check(route, v, d, D, 3, 65, edges=[3, 10, 10, 67, 68], what="254 libraries, edges")
+
+
+def test_an_edge_one_behind_a_window_of_more_than_100000_positions(route):
+    """BRC_BINS_OUTSIDE for an edge at k0 + n + 1, and none for an edge at k0 + n, when the window has 100 001 positions"""
+    Pn = 100002
+    depth = (np.arange(Pn) % 11).astype(np.uint32)[None, :]
+    cnt = np.zeros((1, 4, Pn), np.uint32); cnt[0, 0] = depth[0]
+    v, d, D, keep = hand(route, depth, cnt, b"A" * Pn)
+    n = Pn - 1
+    check(route, v, d, D, 0, n, edges=[0, 50000, n], what="edges up to k0 + n", n_hist=4)
+    check(route, v, d, D, 0, n, edges=[0, 50000, n + 1], what="an edge at k0 + n + 1", n_hist=4, status=capi.BINS_OUTSIDE)
+    check(route, v, d, D, 1, n, edges=[0, 50000, n + 1], what="an edge at k0 - 1", n_hist=4, status=capi.BINS_OUTSIDE)
+
+
+def test_uniform_bins_behind_window_element_2_to_the_24(route):
+    """a window of 2^24 + 5 positions in bins of 2^23: the last five positions are bin 2 (an element index that passes 2^24 has no
+    exact fp32 form).  covered and hist alone read the depth plane alone, so the view's other planes are the depth plane again: 64 MiB."""
+    Pn = 2 ** 24 + 5
+    PS = Pn + 59
+    depth = (np.arange(PS, dtype=np.uint32) % 7).astype(np.uint32)
+    buf = route.put(depth)
+    p = route.ptr(buf)
+    v = capi.DeviceView(route.mem, 0, 1, 0, Pn, PS, p, p, p, p, None, p, None, 0)
+    d = capi.DeviceIndels(route.mem, 0, 1, 0, Pn, None, 0)
+    rc, st, gs, gc, gh = call(route, v, d, 0, Pn, 2 ** 23, thr=(0, 3), n_hist=5, want=("covered", "hist", "status"))
+    assert rc == 0 and st == 0 and untouched(gs)
+    dd = depth[:Pn]
+    cuts = [0, 2 ** 23, 2 ** 24, Pn]
+    want = np.array([[int((dd[a:b] >= t).sum()) for a, b in zip(cuts, cuts[1:])] for t in (0, 3)], np.uint64)
+    assert want[0].tolist() == [2 ** 23, 2 ** 23, 5]
+    assert np.array_equal(gc[0, :, :3], want) and untouched(gc[:, :, 3:])
+    assert np.array_equal(gh[0], np.bincount(np.minimum(dd, 4), minlength=5).astype(np.uint64))
+
+
+def test_reads_in_the_buckets_that_are_no_base(route):
+    """reads in bucket 0 ('=') and bucket 5 (N), in slots and in third-allele records, at positions whose reference is A, C, G or T and
+    at positions whose reference is N (test_select.raw_views: the compact form written down).  S_NONREF counts buckets 1 .. 4 only —
+    shown on the reference's side against a sum that takes bucket 5, or bucket 0, along — and the buckets' own sums count them all.
+    Records of libraries n_lib, n_lib + 1 and -1 lie beside valid ones of the same position and add nothing."""
+    import handmade_views as hv
+    L, Pn = 2, 140
+    k = np.arange(Pn)
+    ref = bytes(b"ACGTN"[x] for x in k % 5)
+    kind = (k // 5) % 4                                     # slots name (ref's, 5), (5, an alternate), (0, ref's), (an alternate, 0)
+    rb = np.where(k % 5 < 4, k % 5 + 1, 1); other = rb % 4 + 1
+    b0 = np.choose(kind, [rb, 5, 0, other]); b1 = np.choose(kind, [5, other, rb, 0])
+    b0[120:130] |= 0x80; b1[130:] |= 0x80                     # bytes 0x80 .. 0x85 name no bucket: those slots' reads count nowhere
+    slotid = np.broadcast_to((b0 | (b1 << 8)).astype(np.uint32), (L, Pn)).copy()
+    si = np.zeros((L, 2, 9, Pn), np.uint32)
+    si[0, 0, 0] = 10 + k % 7; si[0, 1, 0] = 3 + k % 4; si[1, 0, 0] = 2 + k % 3; si[1, 1, 0] = 20 + k % 5
+    recs = []
+    for x in range(0, Pn, 3):                                # a third-allele record of bucket 5 or 0 where no slot names it, every third position
+        b = 0 if b0[x] == 5 or b1[x] == 5 else 5
+        recs.append(hv.record(x, x % L, b, [40 + x % 9] * 9, [0] * 4))
+        if x % 2:
+            recs.append(hv.record(x, x % L, 5 - b, [60 + x % 4] * 9, [0] * 4))      # ... and one that takes a slot's place
+    for x in (7, 63, 64):
+        for bad in (L, L + 1, -1):
+            recs += [hv.record(x, bad, 5, [1000] * 9, [0] * 4), hv.record(x, bad, 2, [1000] * 9, [0] * 4)]
+        recs += [hv.record(x, 0, 6, [1000] * 9, [0] * 4), hv.record(x, 1, 0xFF, [1000] * 9, [0] * 4)]      # buckets that do not exist
+        recs += [hv.record(x, 0, 0x83, [1000] * 9, [0] * 4), hv.record(x, 1, 0x80, [1000] * 9, [0] * 4)]
+    good = [(7, 0, 2, 3), (63, 1, -1, 4), (64, 0, -2, 5)]
+    ind = good + [(x, bad, ln, 1000) for x in (7, 63, 64) for bad in (L, L + 1, -1) for ln in (3, -3)]
+    depth = np.full((L, Pn), 90, np.uint32)
+    v, d, istat, _, refbase, keep = ts.raw_views(route, depth, slotid, si, records=recs[::-1], indels=ind[::-1], ref=ref)
+    D = Dense(depth, depth, istat[:, :, 0, :], refbase, good, 0)
+    assert D.cnt[:, 0].any() and D.cnt[:, 5].any() and D.cnt[:, 5, k % 5 < 4].any() and D.cnt[:, 5, k % 5 == 4].any() and D.cnt.max() < 1000
+    for kw in (dict(width=1), dict(width=5), dict(width=64), dict(k0=3, n=130, edges=[3, 60, 64, 65, 133])):
+        w = check(route, v, d, D, what="buckets 0 and 5, %r" % (kw,), **kw)
+    w = reference(D, 0, Pn, width=Pn)["sums"][:, :, 0]
+    acgt = (k % 5 < 4)
+    for l in range(L):
+        own = D.cnt[l, 1:5][ts._REFCODE[np.frombuffer(refbase, np.uint8)], k].astype(np.uint64)[acgt].sum()
+        assert w[l, 8] == D.cnt[l, 1:5, acgt.nonzero()[0]].sum() - own
+        assert w[l, 8] + D.cnt[l, 5, acgt].sum() != w[l, 8] != w[l, 8] + D.cnt[l, 0, acgt].sum()
+        assert w[l, 2] == D.cnt[l, 0].sum() and w[l, 7] == D.cnt[l, 5].sum()
 
 
 # ------------------------------------------------------------------------------------------------ 6. a site-list axis

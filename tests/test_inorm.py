@@ -238,7 +238,7 @@ def expected(W, T, cap, acap, want=EVERY):
 # ------------------------------------------------------------------------------------------------ calling the library
 
 def call(route, V, T, k0=0, n=None, max_shift=1024, cap=0, acap=0, want=EVERY, rep=None, stride=None, handle=True, view=True, params=True, source=True,
-         ws=True, wsb=None, reserved=(0, 0, 0), dview=None, sfields=None):
+         ws=True, wsb=None, reserved=(0, 0, 0), dview=None, sfields=None, ws_zero=False):
     """brc_inorm_table into sentinel-filled buffers PAD elements wider than the caps and a scratch of exactly brc_inorm_workspace bytes;
     view, table and destinations in the route's memory.  -> (rc, {name: words})"""
     n = V.n_pos - k0 if n is None else n
@@ -267,6 +267,8 @@ def call(route, V, T, k0=0, n=None, max_shift=1024, cap=0, acap=0, want=EVERY, r
     assert need % 4 == 0
     wsb = need if wsb is None else wsb
     bw = route.sentinel(max(wsb, 0) // 4)
+    if ws_zero:                                             # (a caller's scratch may hold anything: zeros instead of 0xA5)
+        bw[:] = 0
     a = {k: (route.ptr(b) if k in want else None) for k, b in buf.items()}
     rc = route.inorm.lib.brc_inorm_table(route.inorm.h if handle else None, C.byref(d) if view else None, C.byref(par) if params else None,
                                          C.byref(S) if source else None, k0, n, route.ptr(bw) if ws else None, max(wsb, 0), a["counts"], a["npos"], a["shift"],
@@ -282,7 +284,7 @@ def untouched(got):
     return all((g == (SENT8 if k == "alleles" else SENT)).all() for k, g in got.items())
 
 
-def check(route, V, T, k0=0, n=None, max_shift=1024, what="", want=EVERY, short=(0, 0), rep=None, stride=None, W=None):
+def check(route, V, T, k0=0, n=None, max_shift=1024, what="", want=EVERY, short=(0, 0), rep=None, stride=None, W=None, ws_zero=False):
     """one call against the reference, bit for bit, sentinels included; the properties first.  short: how far cap / alleles_cap stay
     below the counts.  Returns the reference's result."""
     if W is None:
@@ -290,7 +292,7 @@ def check(route, V, T, k0=0, n=None, max_shift=1024, what="", want=EVERY, short=
         props(V, T, W, max_shift)
     mm, nb = len(W["merged"]), sum(len(g["text"]) for g in W["merged"])
     cap, acap = max(mm + PAD - short[0] * (PAD + 1), 0), max(nb + PAD - short[1] * (PAD + 1), 0)
-    rc, got = call(route, V, T, k0, n, max_shift, cap, acap, want, rep, stride)
+    rc, got = call(route, V, T, k0, n, max_shift, cap, acap, want, rep, stride, ws_zero=ws_zero)
     assert rc == 0, (what, route.inorm.lib.brc_inorm_last_error(route.inorm.h))
     e = expected(W, T, cap, acap, want)
     for k in e:
@@ -420,6 +422,98 @@ def test_records_that_are_not_judged(route):
         B.off[x] = val
         W = check(route, V, B, what="offsets %d" % x)
         assert (W["status"] & NJ) == (0 if (x, val) == (5, 0xFFFFFFF0) else NJ)      # (the last offset clamps to alleles_len: the true one)
+
+
+def test_records_of_libraries_that_do_not_exist(route):
+    """table records whose library is n_lib, n_lib + 1 or -1 beside a valid record of the same position and allele, with 2 libraries
+    and with 254 (the most a view holds): not judged, group -1, BRC_INORM_TABLE_BAD in the status word, and they join no merged record"""
+    ref = b"G" + b"A" * 8 + b"CGTTTTG"
+    s = sums(6)
+    for L in (2, 254):
+        V = View(ref, pos0=50, n_lib=L)
+        recs = [(55, L - 1, "+A", s), (55, L, "+A", s), (55, L + 1, "+A", s), (55, -1, "+A", s), (58, L - 1, "+A", s), (58, L, "+A", s), (63, L, "-T", s),
+                (63, 0, "-T", s)]
+        W = check(route, V, Tab.of(recs), what="bad libraries of %d" % L)
+        assert W["flags"] == [0, NJ, NJ, NJ, 0, NJ, NJ, 0] and W["group"] == [0, -1, -1, -1, 0, -1, -1, 1] and W["status"] == capi.INORM_TABLE_BAD
+        assert [g["members"] for g in W["merged"]] == [2, 1] and W["merged"][0]["lib"] == L - 1
+
+
+def test_a_deletion_whose_text_is_not_the_reference(route):
+    """a hand-made table may spell a deletion otherwise than the reference does: the walk compares the record's OWN bytes for its first
+    L steps.  -CA behind the fourth of six As: the A matches, the C does not — one step, whatever the reference holds L positions on"""
+    V = View(b"G" + b"A" * 6 + b"TG", pos0=0)
+    for text, shift in ((b"-CA", 1), (b"-CAA", 2), (b"-AA", 4), (b"-TCA", 1)):
+        T = Tab.of([(4, 0, text, sums(5))])
+        W = check(route, V, T, what="deletion %r" % text, W=norm_reference(V, T))      # (no haplotype property: the text is not the reference's)
+        assert W["shift"] == [shift] and W["flags"] == [0], (text, W["shift"])
+
+
+def test_a_scratch_of_zeros(route):
+    """the workspace holds whatever the caller left in it: zeros give what 0xA5 gives, with records that are not judged among the others
+    (the words behind the judged records' entries are then never written) and a class of several members at the end"""
+    ref = b"G" + b"A" * 8 + b"CGTTTTG"
+    V = View(ref, pos0=50, n_lib=2)
+    s = sums(6)
+    for recs in ([(55, 0, "+A", s), (56, 5, "+A", s), (58, 0, "+A", s), (62, 1, "-T", s), (63, 1, "-T", s)],
+                 [(52, 0, "", s, 0), (55, 0, "+A", s), (58, 0, "+A", s)], [(55, 0, "+A", s), (58, 0, "+A", s)]):
+        T = Tab.of(recs)
+        W = check(route, V, T, what="zeros")
+        W0 = check(route, V, T, what="zeros", ws_zero=True, W=W)
+        assert W["merged"][-1]["members"] == 2
+
+
+LONG_SHIFTS = (255, 256, 257, 65535, 65536, 65537)
+
+
+def long_walk_case(u):
+    """One repeat of unit u behind a stopper, 65 537 + 16 characters long.  Per free shift s of LONG_SHIFTS an insertion of one unit
+    behind the repeat's s-th character (its text: the unit as it ends there) and a deletion of the L characters that follow; and one
+    record of either kind placed at the target, the repeat's start, already.  Every record of a kind is the same event: seven records
+    become one.  -> (View, Tab, the index of the repeat's first character)"""
+    L, start = len(u), 5
+    size = max(LONG_SHIFTS) + 16
+    rep = (u * (size // L + 1))[:size]
+    ref = b"GNNNN" + rep + b"NTN"
+    recs = [(start - 1, 0, b"+" + rep[:L], sums(2)), (start - 1, 0, b"-" + rep[:L], sums(3))]
+    for s in LONG_SHIFTS:
+        p = start + s - 1
+        recs.append((p, 0, b"+" + bytes(rep[(s - L + i) % L] for i in range(L)), sums(4 + s % 5)))
+        recs.append((p, 0, b"-" + rep[s:s + L], sums(5 + s % 3)))
+    return View(ref, pos0=0), Tab.of(recs), start
+
+
+def shift_by_comparisons(V, T, r, max_shift):
+    """a second statement of a record's walk that rewrites no text: still one comparison per step, against the text character the
+    step's rotation brings to the end (an insertion) or, behind the deletion's own bytes, the reference's.  test_walks_of_255_to_65537_steps
+    holds it against norm_reference's rewriting walk on walk_case's small shifts and on the long ones."""
+    p, ln = int(T.pos[r]), int(T.len[r])
+    L, t = abs(ln), T.texts()[r][1:]
+    s = 0
+    while s < max_shift and match(V.R(p - s), t[(L - 1 - s) % L] if ln > 0 else (t[L - 1 - s] if s < L else V.R(p - s + L))):
+        s += 1
+    return s
+
+
+@pytest.mark.parametrize("u", [b"AC", b"ACG", b"ACGTTGA"], ids=["L2", "L3", "L7"])
+def test_walks_of_255_to_65537_steps(route, u):
+    """free shifts of 255, 256, 257, 65 535, 65 536 and 65 537 in a window of about 65 560 positions over one repeat, unit length 2, 3
+    and 7, insertions and deletions; max_shift at 2^20 and at exactly the longest free shift (no record stops at the limit: the walk
+    asks for the limit only when another step is possible).  The records that walked merge with the one placed at the target."""
+    Vs, Ts, free = walk_case()
+    assert [shift_by_comparisons(Vs, Ts, r, 1024) for r in range(Ts.m)] == norm_reference(Vs, Ts)["shift"] == [free[r] for r in range(Ts.m)]
+    V, T, start = long_walk_case(u)
+    L = len(u)
+    assert [shift_by_comparisons(V, T, r, capi.INORM_MAX_SHIFT) for r in range(T.m)] == [0, 0] + [s for s in LONG_SHIFTS for _ in (0, 1)]
+    for max_shift in (capi.INORM_MAX_SHIFT, max(LONG_SHIFTS)):
+        W = check(route, V, T, max_shift=max_shift, what="long walks, max_shift %d" % max_shift)
+        assert W["shift"] == [0, 0] + [s for s in LONG_SHIFTS for _ in (0, 1)] and W["status"] == 0 and not any(W["flags"])
+        assert all(x == start - 1 for x in W["npos"]) and [g["members"] for g in W["merged"]] == [7, 7]
+        assert [g["text"] for g in W["merged"]] == [b"+" + u, b"-" + u] and W["merged"][0]["of"][0] == 0 and W["merged"][0]["of"][-1] == 12
+    # the rotation of an insertion's text is by s mod L, with s beyond 2^16 and beyond 2^8: other residues than s mod 2^16 and s mod 2^8 give
+    assert L == 2 or any((s & 0xffff) % L != s % L for s in LONG_SHIFTS) and any((s & 0xff) % L != s % L for s in LONG_SHIFTS)
+    # one step short of the longest walk: that record alone stops at the limit and stays apart
+    W = check(route, V, T, max_shift=max(LONG_SHIFTS) - 1, what="long walks, one step short")
+    assert W["flags"][-2:] == [LIMIT, LIMIT] and not any(W["flags"][:-2]) and [g["members"] for g in W["merged"]] == [6, 6, 1, 1]
 
 
 # ------------------------------------------------------------------------------------------------ 3. merging and order

@@ -622,6 +622,8 @@ def test_control_counts_and_depths_next_to_two_to_the_32(sim_route):
     assert list(wc[[0, 2, 4]]) == [3, U32, 2 ** 31 + 1]
     wf, _, _, _, _ = check(route, v, d, D, T, role=[CASE, CTL], what="2^32, max count", **T_(ctl_max_count=U32 - 1, ctl_frac_num=U32, ctl_frac_den=1))
     assert wf[2] == BIT["CTL_ALLELE"] and wf[4] == 0         # U32 > U32 - 1; (2^31 + 1) * 1 <= U32 * U32
+    wf, _, wc, _, _ = check(route, v, d, D, T, role=[CASE, CTL], what="2^32, max count met exactly", **T_(ctl_max_count=U32, ctl_frac_num=U32, ctl_frac_den=1))
+    assert wf[2] == 0 and wc[2] == U32                       # U32 <= U32: a count of 2^32 - 1 under a limit of 2^32 - 1 passes
     t = T_(ctl_frac_num=2, ctl_frac_den=U32)
     wf, _, _, _, _ = check(route, v, d, D, T, role=[CASE, CTL], what="2^32, fraction", **t)
     assert wf[0] == BIT["CTL_ALLELE"] and not wrapped(3, U32, t)             # 3 * U32 > 2 * U32; in 32 bits 3 * U32 = U32 - 2 <= 2 * U32 = U32 - 1
@@ -907,6 +909,166 @@ def test_254_libraries_with_alternating_roles(route):
     v2 = capi.DeviceView.from_buffer_copy(v); d2 = capi.DeviceIndels.from_buffer_copy(d); v2.n_lib = d2.n_lib = 255
     rc, st, gf, gv, gc, gk = call(route, v2, d2, T, **t)
     assert rc == capi.E_ARG and st == SENT and untouched(gf, gv, gc, gk)
+
+
+# ------------------------------------------------------------------------------------------------ 9b. what a mutation pass of the core left standing
+
+def test_roles_above_the_first_role_words(route):
+    """254 libraries with the roles of test_select.lib_pattern(3) (ignore / case / control; no copy of itself 16 .. 128 libraries
+    further).  Position 3: every library has a record of +AC and ONE control library above 127 — whose role 128 libraries below is not
+    control — has more reads than ctl_max_count: it alone vetoes.  Position 40: records of the case libraries, and one such control
+    library alone is shallower than ctl_min_depth.  A role table indexed modulo 16 .. 128 libraries gives other words — asserted on
+    the reference's side."""
+    L = 254
+    role = ts.lib_pattern(3)
+    assert (IGN, CASE, CTL) == (0, 1, 2)
+    high = [l for l in range(128, L) if role[l] == CTL and role[l - 128] != CTL]
+    cv, cd = high[0], high[-1]
+    assert cv != cd
+    shallow = np.full(48, 30, np.uint32); shallow[40] = 1
+    v, d, D, keep = flat_views(route, L=L, ctl_depth={cd: shallow})
+    T = Tab.of([(3, l, "+AC", sums(9 if l == cv else 2)) for l in range(L)] + [(40, l, "-AC", sums(4)) for l in range(L) if role[l] == CASE])
+    t = T_(ctl_max_count=2, ctl_min_depth=2)
+    wf, wv, wc, wk, _ = check(route, v, d, D, T, [3, 40], None, role, what="role pattern", **t)
+    case = np.array([role[l] == CASE for l in T.lib])
+    assert (wf[~case] == NOT_ASKED).all() and (wf[case & (T.pos == 3)] == BIT["CTL_ALLELE"]).all() and (wc[case & (T.pos == 3)] == 9).all()
+    assert (wf[case & (T.pos == 40)] == BIT["CTL_DEPTH"]).all() and not wk.any()
+    for period in (16, 32, 64, 128):
+        other = reference(D, T, [3, 40], None, ts.folded(role, period), **t)
+        assert not np.array_equal(other[0], wf), period
+    other = reference(D, T, [3, 40], None, ts.folded(role, 128), **t)
+    c128 = np.array([ts.folded(role, 128)[l] == CASE for l in T.lib])
+    # folded by 128 libraries, neither control library is one: no veto at position 3, no shallow control at position 40
+    assert not (other[0][c128 & (T.pos == 3)] & BIT["CTL_ALLELE"]).any() and not (other[0][c128 & (T.pos == 40)] & BIT["CTL_DEPTH"]).any()
+
+
+def test_the_reference_bucket_named_by_both_slots(route):
+    """test_vet.same_bucket_views with the reference's bucket named by both slots (b0 == b1): the reference side of every record is the
+    later slot's floats over the integers that are not zero; tables from position 0 .. 3 put every combination on lanes 63 and 64"""
+    v, d, D, keep = tv.same_bucket_views(route, 1, 2)
+    seen = set()
+    for first in range(4):
+        T = Tab.of([(p, 0, "+AC", sums(6, f=(2.0, 0.0, 1.0, 3.0))) for p in range(first, D.n_pos)])
+        for thr in (MID, dict(MID, min_ref_reads=7, min_ref_mapq=52.0)):
+            wf, wv, wc, wk, _ = check(route, v, d, D, T, np.arange(D.n_pos), what="b0 == b1 from %d" % first, **thr)
+            seen |= set(wf.tolist())
+        assert sorted(wv[1, 60:64].tolist()) == [0.0, 6.0, 9.0, 9.0]                    # cr: the reference bucket's reads
+    assert len(seen) >= 3, seen
+
+
+def bad_library_views(route):
+    """test_vet's view of two libraries whose third-allele records at positions 10, 63 and 64 name libraries n_lib, n_lib + 1 and -1 in
+    the reference's bucket, the other slot's and a third one, beside one valid record each"""
+    L, Pn = 2, 130
+    si = np.zeros((L, 2, 9, Pn), np.uint32); sf = np.zeros((L, 2, 4, Pn), np.float32)
+    si[:, 0] = tv.SLOT_I[0][None, :, None] * 3; si[:, 1] = tv.SLOT_I[0][None, :, None]
+    sf[:, 0] = tv.SLOT_F[0][None, :, None]; sf[:, 1] = tv.SLOT_F[1][None, :, None]
+    recs = []
+    for t, x in enumerate((10, 63, 64)):
+        for bad in (L, L + 1, -1):
+            for b in (1, 2, 3):
+                recs.append(hv.record(x, bad, b, [50 + b] * 9, hv.f32bits([9.0] * 4).tolist()))
+        recs.append(hv.record(x, t % L, 1, [25, 1500, 100, 12, 13, 1, 90, 2600, 150], hv.f32bits([2.0, 1.0, 3.0, 2.5]).tolist()))
+    slotid = ts.high_slot_bytes(np.full((L, Pn), 1 | (2 << 8)))
+    slotid[:, 120:] = 1 | (0x81 << 8)                       # (slot 1's byte 0x81 beside slot 0's 1: the reference's bucket is slot 0's alone)
+    return tv.raw_dense(route, np.full((L, Pn), 30), slotid, si, sf, recs[::-1], b"A" * Pn)
+
+
+def test_records_of_libraries_that_do_not_exist(route):
+    """third-allele records and table records whose library is n_lib, n_lib + 1 or -1, each beside a valid record of the same position
+    (table records 63 and 64 among them): the bad third-allele records change no reference bucket, the bad table records are NO_SITE
+    with BRC_IVET_TABLE_OUT_OF_RANGE in the status word, veto nothing and count in no ctl_count"""
+    v, d, D, keep = bad_library_views(route)
+    assert D.istat[0, 1, 0, 10] == 25 and D.istat[1, 1, 0, 10] == 18 and D.istat[1, 1, 0, 63] == 25
+    at = lambda p: [(p, l, "+AC", sums(c)) for l, c in ((0, 6), (-1, 9), (2, 9), (3, 9), (1, 1))]
+    rows = [(p, 0, "-A", sums(3)) for p in range(0, 10)] + at(10) + [(p, 0, "-A", sums(3)) for p in range(11, 58)] + at(63) + at(64)
+    rows += [(p, 0, "-A", sums(3)) for p in range(65, 70)] + [(p, p % 2, "+AC", sums(4)) for p in (100, 104, 109, 110, 117, 129)]     # (slot bytes with bit 7: ts.high_slot_bytes)
+    T = Tab.of(rows)
+    assert T.lib[63] == -1 and T.lib[64] == 2 and T.pos[63] == T.pos[64] == 63
+    for role in ([CASE, CTL], [CTL, CASE], None):
+        wf, wv, wc, wk, st = check(route, v, d, D, T, [10, 63, 64], None, role, what="bad libraries %r" % (role,), **T_(ctl_max_count=1, min_ref_reads=1))
+        assert st == capi.IVET_TABLE_OUT_OF_RANGE
+        bad = (T.lib < 0) | (T.lib >= 2)
+        assert bad.sum() == 9 and (wf[bad] == NO_SITE).all() and not wv[:, bad].any() and not wc[bad].any()
+        assert wc.max() == (1 if role == [CASE, CTL] else 6 if role == [CTL, CASE] else 0)
+    assert list(wk) == [INS, INS, INS]
+    # a list element one behind the planes (idx == n_pos) is out of range as any other
+    w = check(route, v, d, D, T, [10, 63, 64, D.n_pos], what="idx == n_pos", **T_(min_ref_reads=1))
+    assert w[4] == capi.IVET_TABLE_OUT_OF_RANGE | capi.IVET_LIST_OUT_OF_RANGE and list(w[3]) == [INS, INS, INS, 0]
+
+
+def long_run(p, n, case_at):
+    """n records of one position in a table of four libraries (ROLE4): the case records at case_at = (first, middle, last).  The first
+    one's only matching control record lies at n - 20 (more than 64 records to its right), the last one's at 10 (to its left); the
+    middle one has none: the control records around it spell its text plus one byte under the same len, or its text under another len.
+    Everything else is a control or ignored record of another spelling."""
+    first, mid, last = case_at
+    rows = {first: (0, "+AC", None, 6), n - 20: (1, "+AC", None, 5), last: (0, "+AG", None, 6), 10: (2, "+AG", None, 7), mid: (0, "+AT", None, 6),
+            mid + 1: (1, "+ATG", 2, 9), mid - 1: (2, "+AT", 3, 9), mid + 2: (3, "+AT", None, 9)}
+    assert len(rows) == 8
+    out = []
+    for x in range(n):
+        l, text, ln, c = rows.get(x, (1 + x % 3, "+C" + "ACGT"[x % 4] * (1 + x % 5), None, 8))
+        out.append((p, l, text, sums(c)) + (() if ln is None else (ln,)))
+    return out
+
+
+def test_runs_of_130_and_300_records(route):
+    """one position with 130 table records and one with 300: a run crosses a wave edge and a 256 workgroup edge, and a case record's
+    only matching control record is more than 64 records away on either side"""
+    v, d, D, keep = flat_views(route)
+    rows = [(1, 0, "+AC", sums(6))] * 3 + long_run(5, 130, (0, 65, 129)) + [(6, 0, "+AC", sums(6))] + long_run(9, 300, (0, 150, 299)) + [(11, 1, "+AC", sums(9))]
+    T = Tab.of(rows)
+    assert T.m == 435
+    t = T_(ctl_max_count=1)
+    wf, wv, wc, wk, _ = check(route, v, d, D, T, [1, 5, 6, 9, 11], None, ROLE4, what="long runs", **t)
+    for base, n, (first, mid, last) in ((3, 130, (0, 65, 129)), (134, 300, (0, 150, 299))):
+        assert T.pos[base] != T.pos[base - 1] and T.pos[base + n - 1] != T.pos[base + n]
+        assert wf[base + first] == BIT["CTL_ALLELE"] and wc[base + first] == 5 and wf[base + last] == BIT["CTL_ALLELE"] and wc[base + last] == 7
+        assert wf[base + mid] == 0 and wc[base + mid] == 0
+        assert n - 20 - first > 64 and last - 10 > 64
+    assert list(wk) == [INS, INS, INS, INS, 0]
+    # ... and with the roles turned round the long walks start at the control side's records
+    check(route, v, d, D, T, [5, 9], None, [CTL, CASE, CASE, IGN], what="long runs, roles turned", **t)
+
+
+def table_dict(route, T):
+    """a Tab as the dict tensors.indels returns, in the route's memory"""
+    a = dict(pos=T.pos.astype(np.int32), lib=T.lib.astype(np.int32), len=T.len.astype(np.int32), istat=T.istat.view(np.int32) if route.name == "hip" else T.istat,
+             fstat=T.fstat, allele_off=T.off.view(np.int32) if route.name == "hip" else T.off, alleles=T.alleles)
+    if route.name == "hip":
+        a = {k: route.torch.from_numpy(np.ascontiguousarray(x)).cuda() for k, x in a.items()}
+    return dict(a, m=T.m)
+
+
+def test_record_sums_with_a_base_quality_sum(route):
+    """records whose I_SBQ is not zero (no engine writes one into an indel bucket): the variant's base quality in vals is 0 all the
+    same, VAR_BQ is never set, and tensors.vet_indels gives the same words"""
+    from bam_readcount_amd import tensors
+    v, d, D, keep = flat_views(route)
+    recs = []
+    for p in range(1, 40):
+        i, f = sums(6, f=(1.0, 2.0, 3.0, 4.0))
+        i[8] = 7 * p + 1
+        recs.append((p, p % 2, "+AC" if p % 3 else "-AC", (i, f)))
+    T = Tab.of(recs)
+    assert T.istat[8].all()
+    for role, thr in ((None, MID), ([CASE, CTL, IGN, IGN], EASY)):
+        w = check(route, v, d, D, T, np.arange(1, 40), None, role, what="I_SBQ", **thr)
+        judged = w[0] < NOT_ASKED
+        assert judged.any() and not (w[0][judged] & tv.BIT["VAR_BQ"]).any() and not w[1][capi.VET_V_NAMES.index("var_bq")].any()
+        assert w[1][capi.VET_V_NAMES.index("var_mapq")][judged].all()
+
+        class Views:
+            """what tensors.vet_indels asks an engine for"""
+            _names = None
+
+            def device_view(self):
+                return v
+
+            def device_indels(self):
+                return d
+        check_tensors(route, tensors.vet_indels(Views(), route.ivet, table_dict(route, T), idx=np.arange(1, 40), role=role, **thr), w, "I_SBQ, tensors")
 
 
 def test_refused_calls_write_nothing(route, two_libs):

@@ -689,3 +689,84 @@ def test_calls_under_the_host_sanitizers(sim_route, tmp_path):
     _sanitized(tmp_path, "lib254", v, d, D, [c for combine, cuts in ((MIN, (1, 2)), (SUM, (600, 700, 800))) for c in _calls_of(D, 0, D.n_pos, cuts, combine, LIB254_ROLE, ref_n=True)])
     v, d, D, keepalive = low_views(route)
     _sanitized(tmp_path, "low", v, d, D, [c for k0, n in ts.window_list(D.n_pos) for c in _calls_of(D, k0, n, LOW_CUTS, SUM, ref_n=True)])
+
+
+# ------------------------------------------------------------------------------------------------ 8. what a mutation pass of the core left standing
+
+def test_roles_above_the_first_role_words(route):
+    """254 libraries with a role pattern that is no copy of itself 16, 32, 64 or 128 libraries further (ts.lib_pattern), and one
+    position per library at which that library alone decides the class: depth 10 everywhere, 0 (even libraries: the minimum) or 50
+    (odd ones: the maximum) at position l of library l.  A role table indexed modulo 16 .. 128 libraries gives other classes under
+    MIN, MAX and SUM — asserted on the reference's side."""
+    L = 254
+    role = ts.lib_pattern(2)
+    depth = np.full((L, L), 10, np.uint32)
+    depth[np.arange(L), np.arange(L)] = np.where(np.arange(L) % 2, 50, 0)
+    v, d, D, keepalive = hand(route, depth)
+    n1 = sum(role)
+    for combine, cuts in ((MIN, (5,)), (MAX, (20,)), (SUM, (10 * n1 - 5, 10 * n1 + 5))):
+        w = check(route, v, d, D, cuts=cuts, combine=combine, role=role, what="role pattern %d" % combine, min_runs=20, min_classes=2)
+        c = classes_of(D, 0, L, cuts, combine, role)
+        for period in (16, 32, 64, 128):
+            assert not np.array_equal(c, classes_of(D, 0, L, cuts, combine, ts.folded(role, period))), (combine, period)
+        assert (c[128:] != c[128:].min()).any() and (c[:128] != c[:128].min()).any()          # deciding libraries on both sides of 128
+
+
+def test_one_list_alone_with_a_short_capacity(route):
+    """`end` alone, `start` alone and `cls` alone at cap = total - 1, total and 0: exactly min(total, cap) elements of the one list,
+    nothing else"""
+    v, d, D, keepalive = low_views(route)
+    P = D.n_pos
+    w0, w1, wc, wp = reference(D, 0, P, LOW_CUTS)
+    m = len(w0)
+    assert m > 65
+    want = {"start": w0.astype(np.int32).view(np.uint32), "end": w1.astype(np.int32).view(np.uint32), "cls": wc.astype(np.uint32)}
+    for one in ("end", "start", "cls"):
+        for cap in (m - 1, m, 0):
+            rc, total, gs, ge, gc, gp = call(route, v, None, 0, P, cap, cuts=LOW_CUTS, want=(one,))
+            got = {"start": gs, "end": ge, "cls": gc}
+            t = min(m, cap)
+            assert rc == 0 and total == SENT and untouched(gp), (one, cap)
+            for k, g in got.items():
+                if k == one:
+                    assert np.array_equal(g[:t], want[k][:t]) and untouched(g[t:]), "%s alone, cap %d: %r" % (one, cap, g[max(t - 2, 0):t + PAD])
+                else:
+                    assert untouched(g), (one, cap, k)
+            # ... and with the counts beside it
+            rc, total, gs, ge, gc, gp = call(route, v, None, 0, P, cap, cuts=LOW_CUTS, want=(one, "counts"))
+            g = {"start": gs, "end": ge, "cls": gc}[one]
+            assert rc == 0 and total == m and np.array_equal(g[:t], want[one][:t]) and untouched(g[t:]), (one, cap)
+
+
+def test_the_no_reference_class_with_8_and_15_cuts(route):
+    """BRC_RUNS_REF_N with n_cut = 8 and n_cut = 15: class 9 and class 16 (the last bit of `keep` a call can have) appear, alone too"""
+    P = 200
+    k = np.arange(P)
+    ref = bytes(b"ACGTN"[x] for x in (k // 3) % 5)
+    depth = (k * 7 % 23).astype(np.uint32)
+    v, d, D, keepalive = hand(route, depth, ref)
+    for cuts in (tuple(range(1, 9)), tuple(range(1, 16))):
+        nc = len(cuts)
+        w0, w1, wc, wp = check(route, v, d, D, cuts=cuts, ref_n=True, what="%d cuts, ref_n" % nc, min_runs=20, min_classes=nc)
+        assert (wc == nc + 1).sum() >= 10 and wp[nc + 1] == ref.count(b"N") and (wc == nc).any()
+        x0, x1, xc, xp = check(route, v, d, D, 2, P - 5, cuts=cuts, ref_n=True, keep=1 << (nc + 1), what="%d cuts, the last class alone" % nc, min_runs=10)
+        assert (xc == nc + 1).all()
+        w = check(route, v, d, D, cuts=cuts, what="%d cuts, flag off" % nc, with_d=True)
+        assert w[3][nc + 1] == 0
+
+
+def test_sums_of_one_two_and_three_libraries_beyond_32_bits(route):
+    """three libraries with depths around 2^31 and 2^32 - 1: counted alone a library's sum fits, with two and with three counted it
+    passes 2^32 and a 32-bit sum lands in another class"""
+    P = 70
+    depth = np.ones((3, P), np.uint32)
+    depth[:, 5:15] = [[2 ** 31 + 5], [2 ** 31 + 7], [2 ** 31]]; depth[:, 63:65] = 2 ** 32 - 1; depth[:2, 40:50] = 2 ** 31
+    v, d, D, keepalive = hand(route, depth)
+    cuts = (20, 2 ** 32 - 1)
+    for role in ([1, 0, 0], [1, 1, 0], [0, 1, 1], [1, 1, 1]):
+        w = check(route, v, d, D, cuts=cuts, combine=SUM, role=role, what="sum, roles %r" % role, min_runs=3, min_classes=2)
+        c = classes_of(D, 0, P, cuts, SUM, role)
+        s = D.depth[np.asarray(role) == 1].astype(np.uint64).sum(axis=0)
+        wrapped = np.searchsorted(np.asarray(cuts, np.uint64), s & np.uint64(2 ** 32 - 1), "right")
+        assert (wrapped != c).any() == (sum(role) > 1), role
+        assert c[63] == (2 if sum(role) > 0 else 0) and c[5] == (2 if sum(role) > 1 else 1)

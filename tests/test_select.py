@@ -239,6 +239,35 @@ def build_views(route, depth, cnt, ref=None, ref_lo=0, ref_len=None, indels=(), 
     return v, d, Dense(depth, cnt, bytes(refbase), list(indels), pos0), keep
 
 
+def raw_views(route, depth, slotid, si, sf=None, records=(), indels=(), ref=None, pos0=0):
+    """The compact form written down, nothing derived and nothing shuffled: depth, slotid [L, P], si [L, 2, 9, P], sf [L, 2, 4, P]
+    (float32), third-allele records (handmade_views.record) and indel records (pos, lib, len, count) in the order given, libraries
+    outside [0, L) included; ref: the reference characters of the P positions.  Returns (view, indels view, istat [L, 6, 9, P],
+    fstat [L, 6, 4, P] float32 — what the view expands to by handmade_views.expand_reference, the plain loops — refbase, keepalive)."""
+    import handmade_views as hv
+    depth = np.asarray(depth, np.uint32)
+    L, Pn = depth.shape
+    sf = np.zeros((L, 2, 4, Pn), np.float32) if sf is None else np.ascontiguousarray(sf, np.float32)
+    A = {"ncol": depth, "depth": depth, "slotid": np.asarray(slotid, np.uint32), "si": np.asarray(si, np.uint32), "sf": sf.view(np.uint32), "unavail": None}
+    v, keep = hv.make_view(route, A, list(records), pos0=pos0)
+    want = hv.expand_reference(A, list(records))
+    istat = want["istat"].reshape(L, 6, 9, Pn); fstat = want["fstat"].view(np.float32).reshape(L, 6, 4, Pn)
+    srec = np.zeros((len(indels), 18), np.uint32)
+    for r, (p, l, ln, c) in enumerate(indels):
+        srec[r, 0], srec[r, 1], srec[r, 2], srec[r, 5] = np.int64(p) & U32, np.int64(l) & U32, np.int64(ln) & U32, c
+    keep["slots"] = route.put(srec); keep["one"] = route.put(np.zeros(8, np.uint8))
+    d = capi.DeviceIndels(route.mem, 0, L, pos0, Pn, route.ptr(keep["slots"]) if len(indels) else None, len(indels))
+    if len(indels):
+        d.seq4 = d.seq_off = d.l_qseq = route.ptr(keep["one"])
+    refbase = b"N" * Pn
+    if ref is not None:
+        assert len(ref) == Pn
+        keep["ref"] = route.put(np.frombuffer(bytes(ref), np.uint8))
+        d.ref, d.ref_lo, d.ref_hi, d.ref_len = route.ptr(keep["ref"]), pos0, pos0 + Pn, pos0 + Pn
+        refbase = bytes(ref)
+    return v, d, istat, fstat, refbase, keep
+
+
 def low_depth(P, L=2, seed=1, alt=0.08, ref=None):
     """dense counts of a low-depth region: depth 0..12, most of it on the reference base, now and then an alternative allele or two"""
     rng = np.random.default_rng(seed)
@@ -549,6 +578,29 @@ LIB254_CALLS = [([1 + (l % 2) for l in range(254)], P_(BOTH, min_depth=3, min_al
                 ([1] + [0] * 252 + [2], P_(BOTH, min_depth=3, min_alt=2, ctl_max_alt=0))]
 
 
+def lib_pattern(mod, L=254):
+    """a per-library value 0 .. mod - 1 from the bits of x = l * 37 % 251, (x >> 1 ^ x >> 4) % mod: the pattern differs from itself
+    shifted by 16, 32, 64 and 128 libraries at a quarter of the libraries or more, so a role or lib_on table that is indexed modulo a
+    power of two gives another table (select, vet, ivet and runs share it)"""
+    pat = [(((l * 37 % 251) >> 1) ^ ((l * 37 % 251) >> 4)) % mod for l in range(L)]
+    for shift in (16, 32, 64, 128):
+        assert sum(pat[l] != pat[l - shift] for l in range(shift, L)) >= (L - shift) // 4, shift
+    return pat
+
+
+def high_slot_bytes(slotid):
+    """slotid [L, 130] with bit 7 set in slot 0's byte at positions 100 .. 109 and in slot 1's byte from 110 on: 0x81 .. 0x85 name no
+    bucket (a mask of seven bits would read them as 1 .. 5), so those slots' sums belong to nothing"""
+    slotid = np.array(slotid, np.uint32)
+    slotid[:, 100:110] |= 0x80; slotid[:, 110:] |= 0x8000
+    return slotid
+
+
+def folded(pat, period):
+    """the table an index folded to `period` libraries reads"""
+    return [pat[l % period] for l in range(len(pat))]
+
+
 def lib254_views(route):
     depth, cnt, ref = low_depth(70, L=254, seed=3, alt=0.02)
     return build_views(route, depth, cnt, ref, indels=[(7, 253, -2, 3), (7, 1, -1, 1), (9, 252, 4, 2)])
@@ -562,6 +614,92 @@ def test_254_libraries_with_alternating_roles(route):
     # one library more is refused
     v2 = capi.DeviceView.from_buffer_copy(v); d2 = capi.DeviceIndels.from_buffer_copy(d); v2.n_lib = d2.n_lib = 255
     assert call(route, v2, d2, None, P_(), 0, 1, 0)[0] == capi.E_ARG
+
+
+def test_roles_above_the_first_role_words(route):
+    """254 libraries with the role pattern of lib_pattern(3) (ignore / case / control, no copy of itself 16 .. 128 libraries further):
+    a role table indexed modulo 16, 32, 64 or 128 libraries selects other positions — asserted on the reference's side"""
+    v, d, dense, keep = lib254_views(route)
+    role = lib_pattern(3)
+    assert sorted(set(role)) == [0, 1, 2]
+    for p in (P_(BOTH, min_depth=3, min_alt=2, ctl_max_alt=1), P_(SNV, min_depth=2, min_alt=3, ctl_max_alt=2, ctl_frac=(1, 3))):
+        idx, why = check(route, v, d, dense, role, p, what="role pattern", proper=True)
+        for period in (16, 32, 64, 128):
+            other = dense.want(folded(role, period), p)
+            assert not (np.array_equal(other[0], idx) and np.array_equal(other[1], why)), period
+
+
+def SAME_BUCKET(m):
+    """(slot 0's reads, slot 1's reads) of the one bucket both slots name"""
+    return [(0, 0), (m, 0), (0, m), (m, m - 1), (m - 1, m)]
+
+
+def test_two_slots_naming_one_bucket(route):
+    """slotid with b0 == b1 (only hand-made views have it): expand_lane's rule is that the later write wins and that an integer is written
+    only where it is not zero, so the bucket's count is slot 1's unless that is zero.  Counts exactly at min_alt and one below, in
+    either order; the bucket is once the reference's own (nothing may be selected) and once an alternate; windows from k0 = 0 .. 4 put
+    every combination on lanes 63 and 64."""
+    m, Pn = 3, 135
+    combos = SAME_BUCKET(m)
+    for what, b in (("the reference's bucket", 1), ("an alternate", 3)):
+        si = np.zeros((1, 2, 9, Pn), np.uint32)
+        for k in range(Pn):
+            si[0, 0, 0, k], si[0, 1, 0, k] = combos[k % 5]
+        v, d, istat, _, refbase, keep = raw_views(route, np.full((1, Pn), 20), np.full((1, Pn), b | (b << 8)), si, ref=b"A" * Pn)
+        dense = Dense(np.full((1, Pn), 20, np.uint32), istat[:, 1:5, 0, :], refbase, [], 0)
+        assert dense.cnt[0, b - 1, :5].tolist() == [0, m, m, m - 1, m]
+        for k0 in range(5):
+            idx, why = check(route, v, d, dense, None, P_(SNV, min_alt=m), k0, Pn - k0, what="%s, k0 %d" % (what, k0), caps=[1])
+            if b == 1:
+                assert len(idx) == 0
+            else:
+                assert sorted(set((idx % 5).tolist())) == [1, 2, 4] and (why == capi.WHY_G).all() and {63 + k0, 64 + k0} & set(idx.tolist())
+
+
+def test_records_of_libraries_that_do_not_exist(route):
+    """third-allele records and indel records whose library is n_lib, n_lib + 1 or -1, each beside a valid record of the same position
+    (lanes 10, 63 and 64): the list is what the valid records alone give, and nothing outside the contract is written"""
+    L, Pn = 2, 130
+    import handmade_views as hv
+    si = np.zeros((L, 2, 9, Pn), np.uint32); si[:, 0, 0] = 20; si[:, 1, 0, ::7] = 1
+    slotid = high_slot_bytes(np.full((L, Pn), 1 | (3 << 8), np.uint32))     # slot 1: G, one read every seventh position; 0x83 from 110 on
+    si[:, 1, 0, 112] = 9; si[:, 0, 0, 105] = 9; slotid[:, 105] = 0x83 | 0xFF00             # nine reads in a slot whose byte is 0x83: nobody's
+    recs, ind, good = [], [], []
+    for t, k in enumerate((10, 63, 64)):
+        for bad in (L, L + 1, -1):
+            recs.append(hv.record(k, bad, 3, [9] * 9, [0] * 4)); recs.append(hv.record(k, bad, 4, [9] * 9, [0] * 4))
+            ind += [(k, bad, 2, 9), (k, bad, -2, 9)]
+        recs.append(hv.record(k, t % L, 3, [4] * 9, [0] * 4))
+        ind.append((k, t % L, -1, 4)); good.append((k, t % L, -1, 4))
+    recs = recs[::-1]
+    v, d, istat, _, refbase, keep = raw_views(route, np.full((L, Pn), 25), slotid, si, records=recs, indels=ind, ref=b"A" * Pn)
+    dense = Dense(np.full((L, Pn), 25, np.uint32), istat[:, 1:5, 0, :], refbase, good, 0)
+    for role in (None, [1, 2], [2, 1]):
+        idx, why = check(route, v, d, dense, role, P_(BOTH, min_alt=3, ctl_max_alt=0), what="bad libraries, roles %r" % (role,), proper=True, caps=[1])
+        if role is None:
+            assert idx.tolist() == [10, 63, 64] and (why == (capi.WHY_G | capi.WHY_DEL)).all()
+    check(route, v, d, dense, None, P_(BOTH, min_alt=3), 63, 2, what="bad libraries, lanes 63 and 64 alone")
+
+
+def test_records_one_position_behind_the_window(route, monkeypatch):
+    """a third-allele record and an indel record at k0 + n, inside the planes: neither belongs to the window.  Linked or flagged all the
+    same, they would write the word behind head[] / flag[] — next[0], resp. head[0] — and the records of the window's first position
+    would come out otherwise: record 0 is the window's first position's, record 1 another position's with more reads of another base.
+    On the CPU build the record loop runs in both orders (BRC_SIM_LANES, read by tests/sim_select alone): the word is read back only
+    when it is written last.  The product library does not read the variable: on [hip] the second pass is a plain repeat."""
+    import handmade_views as hv
+    Pn, n = 130, 100
+    si = np.zeros((1, 2, 9, Pn), np.uint32); si[0, 0, 0] = 20
+    recs = [hv.record(0, 0, 3, [5] * 9, [0] * 4), hv.record(50, 0, 4, [7] * 9, [0] * 4), hv.record(n, 0, 2, [9] * 9, [0] * 4)]
+    ind = [(n, 0, 2, 5), (20, 0, 3, 4)]
+    v, d, istat, _, refbase, keep = raw_views(route, np.full((1, Pn), 30), np.full((1, Pn), 1 | (0xFF << 8)), si, records=recs, indels=ind, ref=b"A" * Pn)
+    dense = Dense(np.full((1, Pn), 30, np.uint32), istat[:, 1:5, 0, :], refbase, ind, 0)
+    for order in ("backward", "forward"):
+        monkeypatch.setenv("BRC_SIM_LANES", order)
+        idx, why = check(route, v, d, dense, None, P_(BOTH, min_alt=3), 0, n, what="records at k0 + n, %s" % order, caps=[1])
+        assert idx.tolist() == [0, 20, 50] and why.tolist() == [capi.WHY_G, capi.WHY_INS, capi.WHY_T]
+    idx, why = check(route, v, d, dense, None, P_(BOTH, min_alt=3), 0, n + 1, what="... and inside the window")
+    assert idx.tolist() == [0, 20, 50, n] and why[-1] == capi.WHY_C | capi.WHY_INS
 
 
 # ------------------------------------------------------------------------------------------------ 5. indel rules

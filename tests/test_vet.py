@@ -711,6 +711,112 @@ def test_254_libraries(route):
     assert rc == capi.E_ARG and st == SENT
 
 
+def test_lib_on_above_the_first_words(route):
+    """254 libraries judged by test_select.lib_pattern(2), no copy of itself 16 .. 128 libraries further: a lib_on table indexed modulo
+    32, 64 or 128 libraries judges other libraries — asserted on the reference's side"""
+    v, d, D, keep = lib254_views(route)
+    on = ts.lib_pattern(2)
+    idx = np.arange(0, 70, 3)
+    wf, wk, _, _ = check(route, v, d, D, idx, lib_on=on, what="lib_on pattern", **LIB254_T)
+    assert all((wf[l] == NOT_ASKED).all() == (not on[l]) for l in range(254)) and bits_seen(wf)
+    for period in (32, 64, 128):
+        other = reference(D, idx, lib_on=ts.folded(on, period), **LIB254_T)
+        assert not np.array_equal(other[0][128:], wf[128:]) and not np.array_equal(other[1], wk), period
+
+
+def raw_dense(route, depth, slotid, si, sf, records, ref):
+    """test_select.raw_views (the compact form written down) and the Dense its plain expansion gives"""
+    v, d, istat, fstat, refbase, keep = ts.raw_views(route, depth, slotid, si, sf, records, ref=ref)
+    return v, d, Dense(np.asarray(depth, np.uint32), istat, fstat, refbase, 0), keep
+
+
+SLOT_I = (np.array([6, 300, 200, 4, 2, 1, 120, 700, 180], np.uint32), np.array([9, 500, 0, 5, 4, 0, 250, 0, 300], np.uint32))
+SLOT_F = (np.array([1.5, 2.5, 3.5, 4.5], np.float32), np.array([2.25, 0.75, 5.0, 1.25], np.float32))
+
+
+def same_bucket_views(route, named, other):
+    """both slots of every position name bucket `named`; position k has slot 0 empty or counted (k & 1) and slot 1 empty or counted
+    (k & 2), slot 1 with zeros among its integer sums, and the float sums of the two slots differ everywhere, empty slots included.
+    Bucket `other` comes from a third-allele record."""
+    import handmade_views as hv
+    Pn = 134
+    si = np.zeros((1, 2, 9, Pn), np.uint32); sf = np.zeros((1, 2, 4, Pn), np.float32)
+    k = np.arange(Pn)
+    for s in (0, 1):
+        si[0, s] = SLOT_I[s][:, None] * ((k >> s) & 1).astype(np.uint32)[None, :]
+        sf[0, s] = SLOT_F[s][:, None]
+    recs = [hv.record(x, 0, other, [7, 350, 210, 3, 4, 2, 100, 900, 200], hv.f32bits([3.0, 1.0, 2.0, 5.0]).tolist()) for x in range(Pn)]
+    return raw_dense(route, np.full((1, Pn), 30), np.full((1, Pn), named | (named << 8)), si, sf, recs, b"A" * Pn)
+
+
+def test_two_slots_naming_one_bucket(route):
+    """slotid with b0 == b1: the later write wins, integers are written only where they are not zero, floats always (expand_lane) —
+    so slot 1's float sums stand with slot 0's integer sums wherever slot 1 holds a zero.  The bucket is once the reference's own
+    (A, judged against C from a record) and once the asked alternate (C); lists from 0 .. 3 put every combination on lanes 63 and 64.
+    Values and failure words, bit for bit."""
+    tight = dict(MID, min_depth=1, min_var_count=7, min_var_mapq=52.0, min_ref_mapq=52.0, min_var_readpos=0.3, min_ref_readpos=0.3)
+    for what, named, other in (("the reference's bucket", 1, 2), ("an asked alternate", 2, 1)):
+        v, d, D, keep = same_bucket_views(route, named, other)
+        # what the rule means, on the reference's side: position 3 (both counted), 1 (slot 0 alone), 2 (slot 1 alone), 0 (neither)
+        assert D.istat[0, named, :, 3].tolist() == [9, 500, 200, 5, 4, 1, 250, 700, 300] and D.fstat[0, named, :, 3].tolist() == SLOT_F[1].tolist()
+        assert D.istat[0, named, :, 1].tolist() == SLOT_I[0].tolist() and D.fstat[0, named, :, 1].tolist() == SLOT_F[1].tolist()
+        assert D.istat[0, named, :, 2].tolist() == SLOT_I[1].tolist() and not D.istat[0, named, :, 0].any()
+        seen = 0
+        for first in range(4):
+            idx = np.arange(first, D.n_pos)
+            for t in (MID, tight):
+                wf, wk, wv, _ = check(route, v, d, D, idx, np.full(idx.size, capi.WHY_C), what="%s from %d" % (what, first), **t)
+                seen |= bits_seen(wf)
+            count = wv[0, 1, 1 if named == 1 else 0]                                     # the named bucket's read count in vals (cr or cv)
+            assert sorted(count[60:64].tolist()) == [0.0, 6.0, 9.0, 9.0]
+        assert bin(seen).count("1") >= 3, seen
+
+
+def test_records_of_libraries_that_do_not_exist(route):
+    """third-allele records whose library is n_lib, n_lib + 1 or -1 beside a valid record of the same position (elements 10, 63, 64):
+    fail, keep and vals are what the valid records alone give"""
+    import handmade_views as hv
+    L, Pn = 2, 130
+    si = np.zeros((L, 2, 9, Pn), np.uint32); sf = np.zeros((L, 2, 4, Pn), np.float32)
+    si[:, 0] = SLOT_I[0][None, :, None] * 3; si[:, 1] = SLOT_I[0][None, :, None]; sf[:, 0] = SLOT_F[0][None, :, None]; sf[:, 1] = SLOT_F[1][None, :, None]
+    recs = []
+    for t, x in enumerate((10, 63, 64)):
+        for bad in (L, L + 1, -1):
+            for b in (1, 2, 3):                              # the reference's bucket, the other slot's, a third allele
+                recs.append(hv.record(x, bad, b, [50 + b] * 9, hv.f32bits([9.0] * 4).tolist()))
+        recs.append(hv.record(x, t % L, 3, [5, 200, 100, 2, 3, 1, 90, 600, 150], hv.f32bits([2.0, 1.0, 3.0, 2.5]).tolist()))
+    v, d, D, keep = raw_dense(route, np.full((L, Pn), 30), ts.high_slot_bytes(np.full((L, Pn), 1 | (2 << 8))), si, sf, recs[::-1], b"A" * Pn)
+    assert D.istat[0, 3, 0, 10] == 5 and D.istat[1, 3, 0, 63] == 5 and D.istat[1, 3, 0, 10] == 0 and D.istat[0, 1, 0, 10] == 18
+    t = dict(MID, min_var_count=2, min_var_rl=10.0, min_ref_rl=10.0)
+    for idx in (np.arange(Pn), np.array([10, 10, 63, 64, 64])):
+        wf, wk, wv, _ = check(route, v, d, D, idx, what="bad libraries", **t)
+    assert wv[0, 2, 0, 0] == 5 and wv[1, 2, 0, 0] == 0 and wv[1, 2, 0, 2] == 5
+
+
+def test_strand_and_frequency_of_counts_beyond_2_to_the_24(route):
+    """P + M just above 2^24 and near 2^32 with P odd, counts and depths of that size: V_STRAND and V_FREQ are ONE fp32 division of the
+    converted integers, (float)P / (float)(P + M) — the sum taken in integers.  Adding (float)P and (float)M instead rounds twice:
+    the reference's side shows positions where that gives another quotient.  Hand-made views, so both routes run it."""
+    Pn = 96
+    rng = np.random.default_rng(21)
+    plus = np.concatenate([[2 ** 24 + 1, 2 ** 24 + 3, 2 ** 24 - 1, 2 ** 31 + 1, 2 ** 32 - 1, 2 ** 32 - 3, 2 ** 25 + 1, 3],
+                           rng.integers(2 ** 24, 2 ** 26, 44) | 1, rng.integers(2 ** 31, 2 ** 32, 44) | 1]).astype(np.uint32)
+    minus = np.concatenate([[1, 2 ** 24 + 1, 5, 2 ** 31 - 3, 1, 2 ** 32 - 1, 2 ** 25 + 3, 2 ** 24 + 1],
+                            rng.integers(1, 2 ** 24, 44), rng.integers(1, 2 ** 32, 44)]).astype(np.uint32)
+    si = np.zeros((1, 2, 9, Pn), np.uint32)
+    si[0, 0, 0] = 40; si[0, 0, 3] = 20; si[0, 0, 4] = 20
+    si[0, 1, 0] = plus; si[0, 1, 3] = plus; si[0, 1, 4] = minus
+    depth = np.maximum(plus, minus)[None, :] | np.uint32(2 ** 24 + 2)
+    v, d, D, keep = raw_dense(route, depth, np.full((1, Pn), 1 | (2 << 8)), si, None, (), b"A" * Pn)
+    wf, wk, wv, _ = check(route, v, d, D, np.arange(Pn), np.full(Pn, capi.WHY_C), what="large counts", **T_(min_strand_reads=1, strand_num=1, strand_den=3))
+    S = plus.astype(np.uint64) + minus.astype(np.uint64)
+    assert (S > 2 ** 24).all() and (S > 2 ** 32).sum() > 10 and (plus & 1).all()
+    twice = plus.astype(F32) / (plus.astype(F32) + minus.astype(F32))
+    strand = wv[0, 1, capi.VET_V_NAMES.index("strand")]
+    assert np.array_equal(strand, plus.astype(F32) / S.astype(F32)) and (strand != twice).sum() >= 5, (strand != twice).sum()
+    assert (wf[0, 1] & BIT["STRAND"]).any() and not (wf[0, 1] & BIT["STRAND"]).all()
+
+
 # ------------------------------------------------------------------------------------------------ 6. the contract
 
 def test_each_destination_alone_and_two_calls_identical(route):
