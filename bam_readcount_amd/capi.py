@@ -1184,3 +1184,83 @@ class INorm(_Handle):
     def last_timing(self):
         """kernel seconds (waits for the launches of the last call), bytes asked for and written"""
         return super().last_timing()
+
+
+# ---------------------------------------------------------------- device-side join of computed regions (include/brc_join.h)
+JOIN_LIB = os.path.join(HERE, "csrc", "libbrc_join_hip.so")
+JOIN_EXPORTS = [
+    "brc_join_create", "brc_join_destroy", "brc_join_kind", "brc_join_last_error", "brc_join_workspace", "brc_join_sizes_of", "brc_join_views",
+    "brc_join_last_timing",
+]
+JOIN_MAX_SOURCES, JOIN_MAX_LIB = 16, 254
+JOIN_REF_DIFFERS = 1                                                # bit of the status word
+JOIN_DESTS = ("ncol", "depth", "slotid", "si", "sf", "xagg", "slots", "seq_off", "l_qseq", "seq4", "ref")
+
+
+class JoinSource(C.Structure):
+    """brc_join_source (include/brc_join.h): the two views of one engine"""
+    _fields_ = [("view", C.POINTER(DeviceView)), ("indels", C.POINTER(DeviceIndels))]
+
+
+class JoinDest(C.Structure):
+    """brc_join_dest (include/brc_join.h): the caller's destination buffers"""
+    _fields_ = [(k, C.c_void_p) for k in JOIN_DESTS]
+
+
+class JoinSizes(C.Structure):
+    """brc_join_sizes (include/brc_join.h): what the host knows of a join before it runs"""
+    _fields_ = [("n_lib", C.c_int32), ("has_ref", C.c_int32), ("n_xagg", C.c_uint64), ("n_slots", C.c_uint64), ("ref_lo", C.c_int64), ("ref_hi", C.c_int64),
+                ("ref_len", C.c_int64)] + [(k + "_bytes", C.c_uint64) for k in JOIN_DESTS if k != "seq4"] + [("workspace_bytes", C.c_uint64)]
+
+
+def join_sources(pairs):
+    """[(DeviceView, DeviceIndels | None)] -> a JoinSource array (it holds on to the structs it points to)"""
+    arr = (JoinSource * len(pairs))()
+    for s, (v, d) in enumerate(pairs):
+        arr[s].view = C.pointer(v)
+        if d is not None:
+            arr[s].indels = C.pointer(d)
+    arr._keep = list(pairs)
+    return arr
+
+
+class Join(_Handle):
+    """One handle of a library exporting include/brc_join.h: the product's libbrc_join_hip.so (default; raises when it is not built or
+    there is no device — nothing falls back) or the CPU build of the same per-lane functions (tests/sim_join).  views() takes raw
+    addresses; bam_readcount_amd.tensors.join() is the interface that allocates and returns an engine-like object."""
+
+    PREFIX, EXPORTS, LIB, NAME = "brc_join", JOIN_EXPORTS, JOIN_LIB, "join"
+    PROTOS = {"brc_join_workspace": (C.c_size_t, [C.c_uint64]),
+              "brc_join_sizes_of": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(JoinSizes)]),
+              "brc_join_views": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.POINTER(JoinDest), C.POINTER(DeviceView),
+                                           C.POINTER(DeviceIndels), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])}
+
+    def workspace(self, n_slots):
+        """bytes of scratch a join with n_slots joined indel records needs"""
+        return int(self.lib.brc_join_workspace(n_slots))
+
+    def sizes_raw(self, sources, pos0, n_pos, stride):
+        """brc_join_sizes_of as it is -> (the code, JoinSizes); sources: a JoinSource array (join_sources) or None"""
+        z = JoinSizes()
+        return self.lib.brc_join_sizes_of(len(sources) if sources is not None else 0, sources, pos0, n_pos, stride, C.byref(z)), z
+
+    def sizes(self, sources, pos0, n_pos, stride):
+        rc, z = self.sizes_raw(sources, pos0, n_pos, stride)
+        if rc != 0:
+            raise BrcError("brc_join_sizes_of: %d" % rc)
+        return z
+
+    def views_raw(self, sources, pos0, n_pos, stride, dest=None, out_view=None, out_indels=None, counts=None, seq_cap=0, status=None, workspace=None,
+                  workspace_bytes=0, stream=None, K=None):
+        """brc_join_views as it is: dest a JoinDest of addresses (or None: the counts alone), out_view / out_indels the host structs it
+        fills in (or None), counts, status and workspace addresses in memory of the views' kind; returns the code."""
+        K = (len(sources) if sources is not None else 0) if K is None else K
+        return self.lib.brc_join_views(self.h, K, sources, pos0, n_pos, stride, _ref(dest), _ref(out_view), _ref(out_indels), counts, seq_cap, status,
+                                       workspace, workspace_bytes, stream)
+
+    def views(self, sources, pos0, n_pos, stride, **kw):
+        self._check("brc_join_views", self.views_raw(sources, pos0, n_pos, stride, **kw))
+
+    def last_timing(self):
+        """kernel seconds (waits for the launches of the last call), bytes read and written"""
+        return super().last_timing()

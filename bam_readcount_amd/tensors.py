@@ -49,6 +49,12 @@ text, so it runs with the control libraries ignored:
     r = tensors.vet_indels(eng, capi.IVet(), tensors.indels(eng, capi.Indels()), idx=sel["idx"], why=sel["why"], role=[1, 2])
 An aligner may place one indel anywhere inside a repeat: normalize_indels() left-aligns the table and merges what became equal first:
     norm = tensors.normalize_indels(eng, capi.INorm(), tensors.indels(eng, lib)); r = tensors.vet_indels(eng, ivet, norm, role=[1, 2])
+
+A tumour and its normal are usually two files, hence two engines: join() copies the computed regions of several engines into ONE
+engine-like object — the libraries of the second behind those of the first — that every function above takes in an engine's place,
+by libbrc_join_hip.so (capi.Join):
+    both = tensors.join([tumour_eng, normal_eng], capi.Join(), names=["tumour", "normal"])
+    sel = tensors.select(both, select, case=["tumour"], control=["normal"], min_depth=10, min_alt=3)
 """
 from functools import lru_cache, partial
 
@@ -267,7 +273,7 @@ def _library_names(engine, n_lib, who):
     return names
 
 
-# ------------------------------------------------------------------------------------------------ the eight entry points
+# ------------------------------------------------------------------------------------------------ the entry points
 
 KINDS = ("istat", "fstat", "metrics", "depth", "ncol", "unavail")
 DEFAULT_WANT = ("istat", "fstat", "metrics", "depth", "ncol")
@@ -999,3 +1005,100 @@ def normalize_indels(engine, inorm, table, *, max_shift=1024, want=INORM_KINDS):
         call(cap=0, alleles_cap=0)
     del held
     return dict({"m": mm, "first": first, "n": n, "src": per, "status": status}, **arrays)
+
+
+class Joined:
+    """What join() returns: the joined region as every function of this module asks an engine for it — device_view(),
+    device_indels(), _names — over arrays this object holds (`arrays`: capi.JOIN_DESTS -> array; `status`: one uint32 element,
+    capi.JOIN_REF_DIFFERS; `counts`: kept indel records, bytes of seq4).  close() lets the arrays go."""
+
+    def __init__(self, view, indels, names, arrays, status, counts):
+        self._view, self._indels, self._names, self.arrays, self.status, self.counts = view, indels, names, arrays, status, counts
+
+    def _copy(self, v):
+        if self.arrays is None:
+            raise capi.BrcError("the joined region was closed")
+        c = type(v)()
+        capi.C.memmove(capi.C.byref(c), capi.C.byref(v), capi.C.sizeof(v))
+        return c
+
+    def device_view(self):
+        return self._copy(self._view)
+
+    def device_indels(self):
+        return self._copy(self._indels)
+
+    def close(self):
+        self.arrays = self.status = None
+
+
+def join(engines, join, names=None, beg0=None, end=None):
+    """The last computed regions of several engines — two BAM files, a tumour and its normal — COPIED into one region: the libraries of
+    engines[s] become the libraries behind those of engines[:s], over the window [beg0, end) (None: from the first / to the last
+    position any engine has; the window is NOT clipped: where an engine has no planes its libraries are empty positions).  include/
+    brc_join.h has the exact rule: 116 bytes per position and library copied once by libbrc_join_hip.so (capi.Join), third-allele and
+    indel records relabelled, one synthetic read per indel record that spells what the source's read spelled, the reference slices
+    merged.
+
+    names: one label per engine (default "0", "1", ...): the libraries of a joined engine are called `label` (an engine that counts
+    all libraries as one) or `label/<library name>`.
+
+    Returns a Joined: device_view(), device_indels() and _names as an engine has them, so region(), indels(), sites(), select(),
+    bins(), runs(), vet(), normalize_indels() and vet_indels() take it in an engine's place.  It holds its arrays — torch tensors on
+    the engines' device, filled on torch's current stream, with the HIP libraries; numpy arrays with the CPU builds — and is a COPY:
+    once the stream has run the join (the caller synchronises, as for region()) the engines may begin another region or be closed.
+    Its unavail is absent (0xFFFFFFFF everywhere), rep_read / rep_qpos of its indel records are the join's own.
+
+    SYNCHRONISES ONCE when the engines hold indel records: the bytes of the synthetic reads are data (a first call asks for the
+    counts alone).  ValueError, before anything is queued: no engine or more than capi.JOIN_MAX_SOURCES, engines on different devices, a
+    mix of host and device engines, more than capi.JOIN_MAX_LIB libraries, duplicate labels, an empty window."""
+    engines = list(engines)
+    if not 1 <= len(engines) <= capi.JOIN_MAX_SOURCES:
+        raise ValueError("join: 1 .. %d engines" % capi.JOIN_MAX_SOURCES)
+    labels = [str(s) for s in range(len(engines))] if names is None else [x.decode() if isinstance(x, bytes) else str(x) for x in names]
+    if len(labels) != len(engines) or len(set(labels)) != len(labels):
+        raise ValueError("names: one label per engine, none of them twice")
+    pairs = [(e.device_view(), e.device_indels()) for e in engines]
+    kinds = {(int(v.memory), int(v.device)) for v, _ in pairs}
+    if len({m for m, _ in kinds}) != 1:
+        raise ValueError("join: a mix of engines with results in host and in device memory")
+    if len(kinds) != 1:
+        raise ValueError("join: engines on different devices")
+    lib_names = []
+    for e, (v, _), label in zip(engines, pairs, labels):
+        own = [b.decode() for b in e._names]
+        lib_names += [label] if int(v.n_lib) == 1 and len(own) != 1 else ["%s/%s" % (label, x) for x in _library_names(e, int(v.n_lib), "names")]
+    if len(lib_names) > capi.JOIN_MAX_LIB:
+        raise ValueError("join: %d libraries, more than %d" % (len(lib_names), capi.JOIN_MAX_LIB))
+    lo = min(int(v.pos0) for v, _ in pairs) if beg0 is None else int(beg0)
+    hi = max(int(v.pos0) + int(v.n_pos) for v, _ in pairs) if end is None else int(end)
+    n = hi - lo
+    if n <= 0:
+        raise ValueError("join: the window [%d, %d) is empty" % (lo, hi))
+    mem = _memory(pairs[0][0])
+    src = capi.join_sources(pairs)
+    z = join.sizes(src, lo, n, n)
+    L, S = int(z.n_lib), int(z.n_slots)
+    shp = {"ncol": ((L, n), np.uint32), "depth": ((L, n), np.uint32), "slotid": ((L, n), np.uint32), "si": ((L, 2, capi.NI, n), np.uint32),
+           "sf": ((L, 2, capi.NF, n), np.float32), "xagg": ((int(z.n_xagg), 16), np.uint32), "slots": ((S, 18), np.uint32), "seq_off": ((S,), np.uint64),
+           "l_qseq": ((S,), np.int32), "ref": ((int(z.ref_bytes),), np.uint8)}
+    arrays = {k: mem.empty(*shp[k]) for k in shp}
+    wsb = int(z.workspace_bytes)
+    ws, status = _scratch(mem, wsb), mem.zeros(1, np.uint32)
+    view, indels = capi.DeviceView(), capi.DeviceIndels()
+
+    def call(counts=None, seq_cap=0, seq4=None, **_):
+        if counts is not None:                                    # (the counts alone)
+            join.views(src, lo, n, n, counts=counts, workspace=mem.ptr(ws), workspace_bytes=wsb, stream=mem.stream)
+            return
+        dest = capi.JoinDest(seq4=seq4, **_ptrs(mem, {k: arrays[k] for k in shp}, null_if_empty=True))
+        join.views(src, lo, n, n, dest=dest, out_view=view, out_indels=indels, counts=mem.ptr(counts_out), seq_cap=seq_cap, status=mem.ptr(status),
+                   workspace=mem.ptr(ws), workspace_bytes=wsb, stream=mem.stream)
+    counts_out = mem.zeros(2, np.uint32)
+    if S:                                                         # ONE WAIT: the bytes of the synthetic reads are data
+        _, filled = _sized_by_data(mem, call, 2, lambda kept, nbytes: {"seq4": ((nbytes,), np.uint8)}, ("seq4",), ("kept", "seq_cap"), fill_empty=True)
+        arrays["seq4"] = filled["seq4"]
+    else:                                                         # NOTHING SYNCHRONISES: no indel record, no read
+        arrays["seq4"] = mem.empty((0,), np.uint8)
+        call(seq_cap=0, seq4=mem.ptr(arrays["seq4"]))
+    return Joined(view, indels, [x.encode() for x in lib_names], arrays, status, counts_out)
