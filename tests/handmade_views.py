@@ -20,11 +20,11 @@ from fractions import Fraction
 import numpy as np
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import SENT, SENT8
 
 U32 = 0xFFFFFFFF
 NONE32 = U32
-SENT8, SENT = 0xA5, 0xA5A5A5A5
 POISON = 0xDEADBEEF                    # what the stride's padding [P, PS) of every source plane holds
 PAD = 3                                # words of every destination behind what the contract lets a call touch
 NB, NI, NF, NM = 6, 9, 4, 13
@@ -32,7 +32,6 @@ I_N, I_SMQ, I_SSE, I_PLUS, I_MINUS, I_NQ2, I_SMMQ, I_SCLIP, I_SBQ = range(9)
 F_SEV, F_SQ2, F_SNM, F_S3P = range(4)
 KINDS = ("ncol", "depth", "unavail", "istat", "fstat", "metrics")
 OOR, DESC = capi.PANEL_OUT_OF_RANGE, capi.PANEL_NOT_ASCENDING
-_CLASSES = {"dense": capi.Dense, "panel": capi.Panel, "indels": capi.Indels}
 
 
 def planes_of(kind, L):
@@ -41,44 +40,6 @@ def planes_of(kind, L):
 
 def f32bits(x):
     return np.asarray(x, np.float32).view(np.uint32)
-
-
-class Route:
-    """The side libraries named in `libs` of one kind — [sim]: tests/sim_*/libbrc_*_sim.so, host memory; [hip]: the product's, device
-    memory through torch — and the memory their views, lists, scratch and destinations live in."""
-
-    def __init__(self, name, libs):
-        self.name = name
-        if name == "hip":
-            import torch
-            self.torch = torch
-        self.mem = capi.MEM_DEVICE if name == "hip" else capi.MEM_HOST
-        for what in libs:
-            if name == "hip":
-                h = _CLASSES[what]()
-            else:
-                d = os.path.join(ROOT, "tests", "sim_" + what)
-                subprocess.check_call(["make", "-s", "-C", d], stderr=subprocess.DEVNULL)
-                h = _CLASSES[what](os.path.join(d, "libbrc_%s_sim.so" % what))
-            assert h.kind() == ("hip-gfx950" if name == "hip" else "sim")
-            setattr(self, what, h)
-
-    def put(self, a):
-        """the array's bytes in this route's memory (never empty: an empty array still has an address)"""
-        a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-        a = a if a.size else np.zeros(4, np.uint8)
-        return self.torch.from_numpy(a.copy()).cuda() if self.name == "hip" else a.copy()
-
-    def sentinel(self, n_bytes):
-        """n_bytes bytes of 0xA5"""
-        return self.put(np.full(max(n_bytes, 4), SENT8, np.uint8))
-
-    def ptr(self, buf):
-        return buf.data_ptr() if self.name == "hip" else buf.ctypes.data
-
-    def host(self, buf):
-        """the buffer's bytes back on the host (hip: a copy on the default stream, behind the launches queued there)"""
-        return buf.cpu().numpy() if self.name == "hip" else buf
 
 
 # ------------------------------------------------------------------------------------------------ the dense / panel view
@@ -107,10 +68,10 @@ def make_view(route, A, records=(), stride=None, pos0=0):
     def planes(a, rows):
         out = np.full((rows, PS), POISON, np.uint32)
         out[:, :P] = np.asarray(a, np.uint32).reshape(rows, P)
-        return route.put(out)
+        return route.copy_bytes(out)
     rec = records_array(records)
     keep = {"ncol": planes(A["ncol"], L), "depth": planes(A["depth"], L), "slotid": planes(A["slotid"], L), "si": planes(A["si"], L * 2 * NI),
-            "sf": planes(A["sf"], L * 2 * NF), "xagg": route.put(rec)}
+            "sf": planes(A["sf"], L * 2 * NF), "xagg": route.copy_bytes(rec)}
     if A.get("unavail") is not None:
         keep["unavail"] = planes(A["unavail"], 1)
     v = capi.DeviceView(route.mem, 0, L, pos0, P, PS, *[route.ptr(keep[k]) for k in ("ncol", "depth", "slotid", "si")],
@@ -182,7 +143,7 @@ def _destinations(route, sizes, skew):
     256-byte boundary"""
     out = {}
     for k, words in sizes.items():
-        buf = route.sentinel(4 * (words + PAD) + (260 if skew else 0))
+        buf = route.sentinel_bytes(4 * (words + PAD) + (260 if skew else 0))
         off = ((-route.ptr(buf)) % 256 + 4) if skew else 0
         assert not skew or (route.ptr(buf) + off) % 256 == 4
         out[k] = (buf, off)
@@ -212,8 +173,8 @@ def run_panel(route, view, idx, ds, kinds=KINDS, status=True, skew=False):
     L = int(view.n_lib)
     sizes = {k: planes_of(k, L) * ds for k in kinds}
     bufs = _destinations(route, sizes, skew)
-    st = route.sentinel(4)
-    ibuf = route.put(np.asarray(idx, np.int32))
+    st = route.sentinel_bytes(4)
+    ibuf = route.copy_bytes(np.asarray(idx, np.int32))
     rc = route.panel.gather_raw(view, route.ptr(ibuf), len(idx), ds, status=route.ptr(st) if status else None,
                                 **{k: route.ptr(b) + off for k, (b, off) in bufs.items()})
     return rc, int(route.host(st)[:4].view(np.uint32)[0]), _collect(route, bufs, sizes, L, ds)
@@ -411,11 +372,9 @@ def read_checked(d, o, L, n, ds):
 
 def run_checker(which, case_bytes, tmp_path, said):
     """make asan in tests/sim_<which>, run <which>_check_asan over the case; returns the result file's bytes"""
-    d = os.path.join(ROOT, "tests", "sim_" + which)
-    subprocess.check_call(["make", "-s", "-C", d, "asan"], stderr=subprocess.DEVNULL)
     open(tmp_path / "case.bin", "wb").write(case_bytes)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(d, which + "_check_asan"), str(tmp_path / "case.bin"), str(tmp_path / "res.bin")], stdout=subprocess.PIPE,
+    p = subprocess.run([side.sim_checker(side.SIDE[which]), str(tmp_path / "case.bin"), str(tmp_path / "res.bin")], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     assert p.stdout.decode().strip() == said
@@ -461,9 +420,9 @@ def indel_arrays(slots, reads=(), ref=None, ref_lo=0, ref_len=None, pos0=0, n_po
 def make_indels(route, I):
     """-> (capi.DeviceIndels, keep-alive buffers): every source array has exactly its own size, but the reference slice, which has
     one byte 'Z' behind it: a read at ref_hi spells it (the sanitizer programs get the slice alone)"""
-    keep = {k: route.put(I[k]) for k in ("slots", "seq4", "seq_off", "l_qseq")}
+    keep = {k: route.copy_bytes(I[k]) for k in ("slots", "seq4", "seq_off", "l_qseq")}
     if I["ref"] is not None:
-        keep["ref"] = route.put(np.frombuffer(I["ref"] + b"Z", np.uint8))
+        keep["ref"] = route.copy_bytes(np.frombuffer(I["ref"] + b"Z", np.uint8))
     S = len(I["slots"])
     v = capi.DeviceIndels(route.mem, 0, I["n_lib"], I["pos0"], I["n_pos"], route.ptr(keep["slots"]) if S else None, S, route.ptr(keep["seq4"]),
                           route.ptr(keep["seq_off"]), route.ptr(keep["l_qseq"]), I["n_reads"], route.ptr(keep["ref"]) if I["ref"] is not None else None,

@@ -10,8 +10,8 @@ def test_bins_exports_equal_the_header_and_the_binding():
     side.check_exports(ROW)
 
 
-def test_bins_params_layout_and_constants_are_the_headers():
-    side.check_bins_params()
+def test_bins_params_layout_and_constants_are_the_headers(tmp_path):
+    side.check_bins_params(tmp_path)
 
 
 def test_bins_library_has_a_kernel_object_of_its_own():

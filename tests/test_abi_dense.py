@@ -10,8 +10,8 @@ def test_dense_exports_equal_the_header_and_the_binding():
     side.check_seam("brc_device_view_get")
 
 
-def test_view_struct_of_the_binding_has_the_header_layout():
-    side.check_view_struct()
+def test_view_struct_of_the_binding_has_the_header_layout(tmp_path):
+    side.check_view_struct(tmp_path)
 
 
 def test_dense_library_has_a_kernel_object_of_its_own():

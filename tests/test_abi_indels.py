@@ -10,8 +10,8 @@ def test_indels_exports_equal_the_header_and_the_binding():
     side.check_seam("brc_device_indels_get", exported_by_the_engines=True)
 
 
-def test_indels_struct_of_the_binding_has_the_header_layout():
-    side.check_indels_struct()
+def test_indels_struct_of_the_binding_has_the_header_layout(tmp_path):
+    side.check_indels_struct(tmp_path)
 
 
 def test_indels_library_has_a_kernel_object_of_its_own():

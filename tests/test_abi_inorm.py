@@ -1,68 +1,36 @@
 """The indel normalisation is a library of its own: it exports exactly what its header declares and the binding lists, its parameter
 and source structs have the header's layout, its flag and status bits are the header's, it carries a kernel object of its own, leaves
 the engine's kernel object and those of the indel table, the candidate filter and the indel candidate filter what they were, and the
-product library neither links nor loads it.  Its row of the side libraries' table is defined here and handed to the checks of
-tests/abi_side.py, which take any row; "the others" of this row are the engine, the inflater, the deflater and every row of that table."""
+product library neither links nor loads it."""
 import ctypes as C
 import os
-import re
-import subprocess
-
-import pytest
 
 import abi_side as side
-import test_abi_side
+from abi_side import define
 
-ROW = dict(name="inorm", cls="INorm", tensors="normalize_indels",
-           kernels=("k_inorm_shift", "k_inorm_place", "k_inorm_rank", "k_inorm_heads", "k_inorm_merge", "k_side_scan_reduce", "k_side_scan_parts", "k_side_scan_apply"),
-           strict=True, null_call=lambda o: o.table_raw(None, None, None, 0, 1))
+ROW = side.SIDE["inorm"]
 
 
 def test_inorm_exports_equal_the_header_and_the_binding():
     side.check_exports(ROW)
-    from bam_readcount_amd import capi
-    for other in ("IVET_EXPORTS", "VET_EXPORTS", "RUNS_EXPORTS"):          # (the libraries that came after abi_side's table)
-        assert not set(capi.INORM_EXPORTS) & set(getattr(capi, other))
-
-
-def _c_layout(tmp_path, struct, names):
-    src = '#include <stddef.h>\n#include <stdio.h>\n#include "brc_inorm.h"\nint main(void) { printf("%%zu", sizeof(%s));\n' % struct
-    src += "".join('printf(" %%zu", offsetof(%s, %s));\n' % (struct, n) for n in names) + "return 0; }\n"
-    exe = str(tmp_path / (struct + "_layout_check"))
-    subprocess.run(["gcc", "-x", "c", "-std=c99", "-I", os.path.join(side.ROOT, "include"), "-", "-o", exe], input=src.encode(), check=True)
-    return [int(x) for x in subprocess.run([exe], stdout=subprocess.PIPE, check=True).stdout.split()]
-
-
-def _members(h, struct):
-    """the member names of a struct of the header, in order"""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), h, flags=re.S).group(1)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            names += [n.strip().lstrip("*").split("[")[0] for n in re.sub(r"^(const\s+)?\w+\s*\*?", "", decl, count=1).split(",")]
-    return names
 
 
 def test_inorm_structs_and_constants_are_the_headers(tmp_path):
     from bam_readcount_amd import capi
     h = side._header("brc_inorm.h")
     P, S = capi.INormParams, capi.INormSource
-    assert _members(h, "brc_inorm_params") == [n for n, _ in P._fields_] == ["max_shift", "reserved"]
-    assert _c_layout(tmp_path, "brc_inorm_params", ["max_shift", "reserved"]) == [C.sizeof(P), P.max_shift.offset, P.reserved.offset] == [16, 0, 4]
-    names = [n for n, _ in S._fields_]
-    assert _members(h, "brc_inorm_source") == names == ["m", "stride", "pos", "lib", "len", "rep_read", "rep_qpos", "istat", "fstat", "allele_off", "alleles", "alleles_len"]
+    side.check_struct(tmp_path, "brc_inorm.h", "brc_inorm_params", P, array_len=3)
+    assert [n for n, _ in P._fields_] == ["max_shift", "reserved"] and [C.sizeof(P), P.max_shift.offset, P.reserved.offset] == [16, 0, 4]
+    side.check_struct(tmp_path, "brc_inorm.h", "brc_inorm_source", S)
+    assert [n for n, _ in S._fields_] == ["m", "stride", "pos", "lib", "len", "rep_read", "rep_qpos", "istat", "fstat", "allele_off", "alleles", "alleles_len"]
     for n, ct in S._fields_:
         assert ct is (C.c_int64 if n in ("m", "stride", "alleles_len") else C.c_void_p), n
-    assert _c_layout(tmp_path, "brc_inorm_source", names) == [C.sizeof(S)] + [getattr(S, n).offset for n in names] and C.sizeof(S) == 96
-
-    def define(name):
-        return int(re.search(r"#define\s+%s\s+(\d+)u?\b" % name, h).group(1))
-    assert define("BRC_INORM_MAX_SHIFT") == capi.INORM_MAX_SHIFT == 1 << 20
+    assert C.sizeof(S) == 96
+    assert define(h, "BRC_INORM_MAX_SHIFT") == capi.INORM_MAX_SHIFT == 1 << 20
     flags = ("NOT_JUDGED", "LIMIT", "EDGE")
-    assert [define("BRC_INORM_" + n) for n in flags] == [getattr(capi, "INORM_" + n) for n in flags] == [1, 2, 4]
+    assert [define(h, "BRC_INORM_" + n) for n in flags] == [getattr(capi, "INORM_" + n) for n in flags] == [1, 2, 4]
     status = ("TABLE_BAD", "ANY_LIMIT", "ANY_EDGE")
-    assert [define("BRC_INORM_" + n) for n in status] == [getattr(capi, "INORM_" + n) for n in status] == [1, 2, 4]
+    assert [define(h, "BRC_INORM_" + n) for n in status] == [getattr(capi, "INORM_" + n) for n in status] == [1, 2, 4]
     # the new table is the indel table's: the same destinations, and one more
     assert capi.INORM_DESTS == capi.INDEL_DESTS[:5] + ("members",) + capi.INDEL_DESTS[5:]
 
@@ -77,9 +45,6 @@ def test_inorm_runs_the_dense_librarys_columns_not_a_copy():
 
 def test_inorm_library_has_a_kernel_object_of_its_own():
     side.check_kernel_object(ROW)
-    from bam_readcount_amd import capi
-    mine = capi.kernel_object_hash(capi.INORM_LIB)
-    assert mine not in [capi.kernel_object_hash(p) for p in (capi.IVET_LIB, capi.VET_LIB, capi.RUNS_LIB)]
 
 
 def test_engine_and_sibling_kernel_objects_are_unchanged():
@@ -96,9 +61,6 @@ def test_engine_and_sibling_kernel_objects_are_unchanged():
 
 def test_product_library_neither_links_nor_loads_the_inorm_library():
     side.check_neither_links_nor_loads(ROW)
-    from bam_readcount_amd import capi
-    for lib in (capi.IVET_LIB, capi.VET_LIB, capi.RUNS_LIB):
-        assert b"brc_inorm" not in open(lib, "rb").read(), lib
 
 
 def test_the_inorm_sources_use_no_inline_assembly_and_the_siblings_flags():
@@ -113,8 +75,3 @@ def test_package_and_inorm_import_without_torch():
 
 def test_inorm_library_refuses_to_exist_without_a_device_or_a_build():
     side.check_refuses_to_exist(ROW)
-
-
-@pytest.mark.parametrize("build", ["sim", pytest.param("hip", marks=pytest.mark.gpu)])
-def test_inorm_handle_lifecycle(build):
-    test_abi_side.test_handle_lifecycle(ROW, build)

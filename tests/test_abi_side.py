@@ -1,10 +1,29 @@
 """The lifecycle every side library shares (brc_side_hip.h for the gfx950 builds, tests/sim_side.h for the CPU builds), library by
 library over the table of tests/abi_side.py; what is a library's own is in tests/test_abi_<library>.py."""
 import ctypes as C
+import os
+import re
 
 import pytest
 
 import abi_side as side
+
+
+def test_the_table_is_every_side_library():
+    """The table's rows, the SIDE list of the build rule, the CPU builds under tests/ and the binding's LIB / EXPORTS pairs name the
+    same ten libraries: one that is built, simulated or bound without a row would escape every sibling check."""
+    from bam_readcount_amd import capi
+    mk = open(os.path.join(side.CSRC, "Makefile")).read()
+    words = lambda var: set(re.search(r"^%s = (.*)$" % var, mk, flags=re.M).group(1).split())
+    codecs = words("CODEC")                                    # (the inflater and the deflater: tests/test_abi_{inflate,deflate}.py)
+    tests = os.path.join(side.ROOT, "tests")
+    sims = {d[4:] for d in os.listdir(tests) if d.startswith("sim_") and os.path.exists(os.path.join(tests, d, "brc_%s_sim.cpp" % d[4:]))}
+    bound = {n[:-4].lower() for n in dir(capi) if n.endswith("_LIB") and hasattr(capi, n[:-4] + "_EXPORTS")}
+    rows = [r["name"] for r in side.ROWS]
+    assert len(rows) == 10 and set(rows) == set(side.SIDE) == words("SIDE") == sims - codecs == bound - codecs
+    assert codecs == {"inflate", "deflate"} and codecs <= sims and codecs <= bound
+    for r in side.ROWS:
+        assert set(r.get("uses", ())) <= set(rows) - {r["name"]}, r["name"]
 
 
 @pytest.mark.parametrize("row", side.ROWS, ids=list(side.SIDE))

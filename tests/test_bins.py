@@ -21,14 +21,13 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import Route, SENT
 import test_dense as td
 import test_select as ts
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_bins")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_bins_sim.so")
 SENT64 = np.uint64(0xA5A5A5A5A5A5A5A5)
-SENT = td.SENT
+LIBS = ("dense", "select", "bins")
 PAD = 3                                   # elements of every row behind n_bins
 NSUM = capi.BINS_NSUM
 PER_LIB = ts.PER_LIB
@@ -36,31 +35,14 @@ ALL = ("sums", "covered", "hist", "status")
 THR = (0, 1, 4, 10, 20, 30)
 
 
-class Route(ts.Route):
-    """ts.Route (engine + dense + select libraries, the memory their views live in) with the bins library of the same kind"""
-
-    def __init__(self, name):
-        ts.Route.__init__(self, name)
-        if name == "hip":
-            self.bins = capi.Bins()
-            assert self.bins.kind() == "hip-gfx950"
-        else:
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            self.bins = capi.Bins(SIM_LIB)
-            assert self.bins.kind() == "sim"
-
-    def quads(self, buf):
-        return self.words(buf).view(np.uint64)
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, LIBS, engine=True)
 
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS, engine=True)
 
 
 # ------------------------------------------------------------------------------------------------ the reference
@@ -143,7 +125,7 @@ def call(route, v, d, k0, n, width=0, edges=None, thr=(), n_hist=0, ds=None, wan
     nb = count_bins(n, width, edges)
     ds = nb + PAD if ds is None else ds
     nt, nh, dd = min(len(thr), 8), min(max(n_hist, 0), 4096), max(ds, 0)
-    bs, bc, bh, bt = route.sentinel(max(2 * (L + 1) * NSUM * dd, 2)), route.sentinel(max(2 * L * nt * dd, 2)), route.sentinel(max(2 * L * nh, 2)), route.sentinel(1)
+    bs, bc, bh, bt = route.sentinel_words(max(2 * (L + 1) * NSUM * dd, 2)), route.sentinel_words(max(2 * L * nt * dd, 2)), route.sentinel_words(max(2 * L * nh, 2)), route.sentinel_words(1)
     be = route.put(np.asarray(edges, np.int32)) if edges is not None else None
     par = capi.bins_params(width, route.ptr(be) if be is not None else None, nb if edges is not None else 0, list(thr), n_hist)
     for k, x in (fields or {}).items():
@@ -658,7 +640,7 @@ def _sanitized(tmp_path, name, v, d, D, calls):
     case, out = str(tmp_path / (name + ".bin")), str(tmp_path / (name + ".res"))
     open(case, "wb").write(_serialize(v, d, calls))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    pr = subprocess.run([os.path.join(SIM_DIR, "bins_check_asan"), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    pr = subprocess.run([side.sim_checker(side.SIDE["bins"]), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert pr.returncode == 0, (name, pr.stderr.decode()[-3000:])
     assert pr.stdout.decode().strip() == "%d calls" % len(calls), name
     raw = open(out, "rb").read(); o = 0
@@ -685,7 +667,6 @@ def test_calls_under_the_host_sanitizers(oracle_lib, sim_route, tmp_path, monkey
     of exactly the views' sizes, an edge list of exactly n_bins + 1 elements, destinations of exactly [.][n_bins + PAD] — a load or
     store outside them is a report — and the results are the reference's.  One engine-made region carries third-allele records."""
     route = sim_route
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
     v, d, D, keep = low_views(route)
     calls = [(k0, n, width, edges, THR, 16, 15) for k0, n, width, edges in window_calls(D.n_pos)]
     for k0, n in ((0, D.n_pos), (37, 1301)):

@@ -14,12 +14,10 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import Route, SENT
 import synth
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_dense")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_dense_sim.so")
-SENT = 0xA5A5A5A5
 KINDS = ("ncol", "depth", "unavail", "istat", "fstat", "metrics")
 
 
@@ -27,53 +25,15 @@ def planes_of(kind, L):
     return {"ncol": L, "depth": L, "unavail": 1, "istat": L * 6 * 9, "fstat": L * 6 * 4, "metrics": L * 6 * 13}[kind]
 
 
-class Route:
-    """One pair of libraries (engine, dense) and the memory their views live in."""
-
-    def __init__(self, name):
-        self.name = name
-        if name == "hip":
-            import torch
-            self.torch = torch
-            self.engine_lib = capi.load_product()
-            # conftest's knob_lib [hip]: the product's own objects linked with the test knobs switched on
-            self.knob_lib = capi.Library(os.path.join(ROOT, "bam_readcount_amd", "csrc", "libbrc_hip_testknobs.so"))
-            self.dense = capi.Dense()
-            assert self.dense.kind() == "hip-gfx950"
-            self.mem = capi.MEM_DEVICE
-        else:
-            subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "sim")])
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            self.engine_lib = capi.Library(os.path.join(ROOT, "tests", "sim", "libbrc_sim.so"))
-            self.knob_lib = self.engine_lib                    # (the simulator reads the knobs itself)
-            self.dense = capi.Dense(SIM_LIB)
-            assert self.dense.kind() == "sim"
-            self.mem = capi.MEM_HOST
-
-    def sentinel(self, n_words):
-        """n_words 32-bit words holding SENT, in the memory of this route's views"""
-        a = np.full(max(n_words, 1), SENT, np.uint32)
-        if self.name == "hip":
-            return self.torch.from_numpy(a.view(np.int32)).cuda()
-        return a
-
-    def ptr(self, buf):
-        return buf.data_ptr() if self.name == "hip" else buf.ctypes.data
-
-    def words(self, buf):
-        """the buffer's words back on the host (hip: a copy on the default stream, behind the launches queued there)"""
-        return buf.cpu().numpy().view(np.uint32) if self.name == "hip" else buf
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, ("dense",), engine=True)
 
 
 def expand(route, view, k0, n, ds, kinds=KINDS):
     """brc_dense_expand into sentinel-filled buffers of [planes][ds]; returns (rc, {kind: uint32 words [planes, ds]})"""
     L = int(view.n_lib) if view is not None and view.n_lib > 0 else 1
-    bufs = {k: route.sentinel(planes_of(k, L) * max(ds, 0)) for k in kinds}
+    bufs = {k: route.sentinel_words(planes_of(k, L) * max(ds, 0)) for k in kinds}
     rc = route.dense.expand_raw(view, k0, n, ds, **{k: route.ptr(b) for k, b in bufs.items()})
     out = {}
     for k, b in bufs.items():
@@ -253,7 +213,7 @@ def _serialize_view(v, windows):
 def test_windows_under_the_host_sanitizers(oracle_lib, sim_lib, tmp_path):
     """The window list on the CPU build with -fsanitize=address,undefined: sources of exactly the view's sizes, destinations of
     exactly (planes - 1) * dst_stride + n elements — a load or store outside them is a report — and the results are the oracle's."""
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
+    checker = side.sim_checker(side.SIDE["dense"])
     ref, arrs = third_allele_inputs()
     opts = dict(lib_names=["libA", "libB"], per_lib=True)
     res, _ = oracle_result(oracle_lib, arrs, 100, 1900, ref, **opts)
@@ -264,7 +224,7 @@ def test_windows_under_the_host_sanitizers(oracle_lib, sim_lib, tmp_path):
     open(tmp_path / "case.bin", "wb").write(_serialize_view(v, wins))
     eng.close()
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(SIM_DIR, "dense_check_asan"), str(tmp_path / "case.bin"), str(tmp_path / "res.bin")],
+    p = subprocess.run([checker, str(tmp_path / "case.bin"), str(tmp_path / "res.bin")],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     assert p.stdout.decode().strip() == "%d windows" % len(wins)

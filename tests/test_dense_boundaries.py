@@ -12,13 +12,14 @@ import numpy as np
 import pytest
 
 import handmade_views as hv
+from route import Route
 
 KINDS = hv.KINDS
 
 
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return hv.Route(request.param, ("dense",))
+    return Route(request.param, ("dense",))
 
 
 _cache = {}

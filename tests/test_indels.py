@@ -19,57 +19,19 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import Route, SENT, SENT8
 import synth
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_indels")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_indels_sim.so")
-SENT8 = 0xA5
-SENT = 0xA5A5A5A5
 DESTS = capi.INDEL_DESTS
 PLANES = dict(pos=1, lib=1, len=1, rep_read=1, rep_qpos=1, istat=9, fstat=4, metrics=13)
 PAD = 3              # elements of every destination behind what the contract lets a call touch
 WAVE, TILE = 64, 256
 
 
-class Route:
-    """One pair of libraries (engine, indels) and the memory their views live in."""
-
-    def __init__(self, name):
-        self.name = name
-        if name == "hip":
-            import torch
-            self.torch = torch
-            self.engine_lib = capi.load_product()
-            self.knob_lib = capi.Library(os.path.join(ROOT, "bam_readcount_amd", "csrc", "libbrc_hip_testknobs.so"))
-            self.indels = capi.Indels()
-            assert self.indels.kind() == "hip-gfx950"
-            self.mem = capi.MEM_DEVICE
-        else:
-            subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "sim")])
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR], stderr=subprocess.DEVNULL)
-            self.engine_lib = capi.Library(os.path.join(ROOT, "tests", "sim", "libbrc_sim.so"))
-            self.knob_lib = self.engine_lib                    # (the simulator reads the knobs itself)
-            self.indels = capi.Indels(SIM_LIB)
-            assert self.indels.kind() == "sim"
-            self.mem = capi.MEM_HOST
-
-    def sentinel(self, n_bytes):
-        """n_bytes bytes of 0xA5 in the memory of this route's views"""
-        a = np.full(max(n_bytes, 4), SENT8, np.uint8)
-        return self.torch.from_numpy(a).cuda() if self.name == "hip" else a
-
-    def ptr(self, buf):
-        return buf.data_ptr() if self.name == "hip" else buf.ctypes.data
-
-    def host(self, buf):
-        """the buffer's bytes back on the host (hip: a copy on the default stream, behind the launches queued there)"""
-        return buf.cpu().numpy() if self.name == "hip" else buf
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, ("indels",), engine=True)
 
 
 def gather(route, view, k0, n, cap, acap, dests=DESTS, counts=True, ws_bytes=None, handle=True):
@@ -78,11 +40,11 @@ def gather(route, view, k0, n, cap, acap, dests=DESTS, counts=True, ws_bytes=Non
     c, a = max(cap, 0), max(acap, 0)
     size = {k: 4 * (PLANES[k] * c + PAD) for k in PLANES}
     size["allele_off"] = 4 * (c + 1 + PAD); size["alleles"] = a + PAD
-    bufs = {k: route.sentinel(size[k]) for k in dests}
-    cbuf = route.sentinel(8)
+    bufs = {k: route.sentinel_bytes(size[k]) for k in dests}
+    cbuf = route.sentinel_bytes(8)
     need = route.indels.workspace(view, n) if view is not None else 0
     wsb = need if ws_bytes is None else ws_bytes
-    ws = route.sentinel(wsb)
+    ws = route.sentinel_bytes(wsb)
     args = {k: route.ptr(b) for k, b in bufs.items()}
     fn = route.indels.lib.brc_indels_gather
     rc = fn(route.indels.h if handle else None, C.byref(view) if view is not None else None, k0, n, route.ptr(ws) if wsb else None, wsb,
@@ -499,7 +461,7 @@ def test_windows_under_the_host_sanitizers(pressure, sim_lib, tmp_path):
     """The window list on the CPU build with -fsanitize=address,undefined: sources of exactly the view's sizes, a scratch of exactly
     brc_indels_workspace bytes and destinations of exactly the contract's sizes on the heap — a load or store outside them is a
     report — exact capacities and capacities one short; the results are the oracle's."""
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"], stderr=subprocess.DEVNULL)
+    checker = side.sim_checker(side.SIDE["indels"])
     ref, arrs, opts, res = pressure
     eng = computed(sim_lib, arrs, 0, RL, ref, **opts)
     v = eng.device_indels()
@@ -513,7 +475,7 @@ def test_windows_under_the_host_sanitizers(pressure, sim_lib, tmp_path):
     open(tmp_path / "case.bin", "wb").write(_serialize(v, calls))
     eng.close()
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(SIM_DIR, "indels_check_asan"), str(tmp_path / "case.bin"), str(tmp_path / "res.bin")],
+    p = subprocess.run([checker, str(tmp_path / "case.bin"), str(tmp_path / "res.bin")],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     assert p.stdout.decode().strip() == "%d calls" % len(calls)

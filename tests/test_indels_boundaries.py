@@ -12,6 +12,7 @@ import pytest
 
 from bam_readcount_amd import capi
 import handmade_views as hv
+from route import Route
 import test_indels as ti
 
 DESTS = ti.DESTS
@@ -20,7 +21,7 @@ TILE = 256
 
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return hv.Route(request.param, ("indels",))
+    return Route(request.param, ("indels",))
 
 
 _cache = {}

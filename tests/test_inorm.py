@@ -22,16 +22,15 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import Route, SENT, SENT8
 import test_dense as td
 import test_indels as ti
 import test_ivet as tiv
 import test_select as ts
 import test_vet as tv
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_inorm")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_inorm_sim.so")
-SENT, SENT8 = 0xA5A5A5A5, 0xA5
+LIBS = tiv.LIBS + ("inorm",)
 PAD = 3
 F32 = np.float32
 NJ, LIMIT, EDGE = capi.INORM_NOT_JUDGED, capi.INORM_LIMIT, capi.INORM_EDGE
@@ -43,28 +42,14 @@ CASE, CTL = capi.ROLE_CASE, capi.ROLE_CONTROL
 Tab, sums = tiv.Tab, tiv.sums
 
 
-class Route(tiv.Route):
-    """tiv.Route (engine, dense, select, vet, ivet and indels libraries, the memory their views live in) with the inorm library of its kind"""
-
-    def __init__(self, name):
-        tiv.Route.__init__(self, name)
-        if name == "hip":
-            self.inorm = capi.INorm()
-            assert self.inorm.kind() == "hip-gfx950"
-        else:
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            self.inorm = capi.INorm(SIM_LIB)
-            assert self.inorm.kind() == "sim"
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, LIBS, engine=True)
 
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS, engine=True)
 
 
 # ------------------------------------------------------------------------------------------------ the view
@@ -261,12 +246,12 @@ def call(route, V, T, k0=0, n=None, max_shift=1024, cap=0, acap=0, want=EVERY, r
         d = dview(d)
     sizes = {"counts": 2, "status": 1, "allele_off": max(cap, 0) + 1}
     sizes.update({k: m for k in PER_IN}); sizes.update({k: max(cap, 0) for k in PER_OUT}); sizes.update({k: f * max(cap, 0) for k, f in PLANES})
-    buf = {k: route.sentinel(sz + PAD) for k, sz in sizes.items()}
-    buf["alleles"] = route.sentinel((max(acap, 0) + PAD + 3) // 4 + 1)
+    buf = {k: route.sentinel_words(sz + PAD) for k, sz in sizes.items()}
+    buf["alleles"] = route.sentinel_words((max(acap, 0) + PAD + 3) // 4 + 1)
     need = route.inorm.workspace(n, m)
     assert need % 4 == 0
     wsb = need if wsb is None else wsb
-    bw = route.sentinel(max(wsb, 0) // 4)
+    bw = route.sentinel_words(max(wsb, 0) // 4)
     if ws_zero:                                             # (a caller's scratch may hold anything: zeros instead of 0xA5)
         bw[:] = 0
     a = {k: (route.ptr(b) if k in want else None) for k, b in buf.items()}
@@ -851,9 +836,7 @@ def test_tensors_normalize_indels_on_text_only_engines_a_site_lists_table_and_it
                 tensors.normalize_indels(eng, route.inorm, b.pop("table", t), **b)
         eng.close()
     # the table of a site list (strided on the host route)
-    if route.name == "sim":
-        subprocess.check_call(["make", "-s", "-C", tp.SIM_DIR])
-    panel = capi.Panel() if route.name == "hip" else capi.Panel(tp.SIM_LIB)
+    panel = route.another("panel")
     ref, arrs, res = repeats
     T = Tab.of_oracle(res.indels)
     eng = td.computed(route.engine_lib, arrs, 50, 2950, ref, **ts.PER_LIB)
@@ -895,7 +878,7 @@ def _sanitized(tmp_path, name, V, calls):
     case, out = str(tmp_path / (name + ".bin")), str(tmp_path / (name + ".res"))
     open(case, "wb").write(_serialize(V, [c[:8] for c in full]))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    pr = subprocess.run([os.path.join(SIM_DIR, "inorm_check_asan"), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    pr = subprocess.run([side.sim_checker(side.SIDE["inorm"]), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert pr.returncode == 0, (name, pr.stderr.decode()[-3000:])
     assert pr.stdout.decode().strip() == "%d calls" % len(calls), name
     raw = np.fromfile(out, np.uint8); o = 0
@@ -921,7 +904,6 @@ def test_calls_under_the_host_sanitizers(sim_route, tmp_path):
     and the table of exactly their sizes, a scratch of exactly brc_inorm_workspace bytes, destinations of exactly the caps — a load or
     store outside them is a report — and the results are the reference's.  Never under the gpu mark; nothing is loaded into python with
     a sanitizer."""
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
     some = 0
     V, T, _ = walk_case()
     some += _sanitized(tmp_path, "walk", V, [(T, 0, None, 1024, 0, None, 15), (T, 0, None, 2, 0, None, 15), (T, 0, None, 0, 1, None, 15), (T, 7, V.n_pos - 20, 1024, 0, None, 15)])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
+from route import Route
 import test_indels as ti
 import test_inorm as tn
 import test_ivet as tiv
@@ -27,15 +28,7 @@ PAD = tss.PAD
 SEED = 21
 
 
-class Route(tss.Route):
-    def __init__(self, name):
-        tss.Route.__init__(self, name)
-        if name == "hip":
-            self.ivet, self.inorm = capi.IVet(), capi.INorm()
-        else:
-            tss.subprocess.check_call(["make", "-s", "-C", tiv.SIM_DIR])
-            tss.subprocess.check_call(["make", "-s", "-C", tn.SIM_DIR])
-            self.ivet, self.inorm = capi.IVet(tiv.SIM_LIB), capi.INorm(tn.SIM_LIB)
+LIBS = tss.LIBS + ("ivet", "inorm")
 
 
 def source_of(route, buf, cap, acap):
@@ -44,12 +37,12 @@ def source_of(route, buf, cap, acap):
 
 def counted(route, sc, gat, cap, acap):
     """the first, untimed call: the gather and brc_inorm_table for its two counts alone, on the default stream; the host reads them"""
-    buf = {k: route.alloc(n) for k, n in gat.sizes(route).items()}
-    buf["n.counts"], buf["n.ws"] = route.alloc(8), route.alloc(route.inorm.workspace(tss.P, cap))
+    buf = {k: route.sentinel_bytes(max(n, 8)) for k, n in gat.sizes(route).items()}
+    buf["n.counts"], buf["n.ws"] = route.sentinel_bytes(8), route.sentinel_bytes(max(route.inorm.workspace(tss.P, cap), 8))
     assert gat.enqueue(route, buf, None) == 0
     route.inorm.table(sc.d, capi.INormParams(1024), source_of(route, buf, cap, acap), 0, tss.P, workspace=route.ptr(buf["n.ws"]),
                       workspace_bytes=route.inorm.workspace(tss.P, cap), counts=route.ptr(buf["n.counts"]))
-    return [int(x) for x in route.bytes_of(buf["n.counts"])[:8].view(np.uint32)]
+    return [int(x) for x in route.host(buf["n.counts"])[:8].view(np.uint32)]
 
 
 def chain_job(sc, expect):
@@ -99,7 +92,7 @@ def cpu_bytes(sim_route, seed):
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS)
 
 
 def test_the_chain_on_the_cpu_builds_is_the_reference(sim_route):
@@ -136,7 +129,7 @@ def gpu(sim_route):
     """The hip route, one scene, the chain run once on the default stream (code objects loaded, the values checked there too, its warm
     host time taken), and the hold sized against it."""
     g = tss.Gpu()
-    g.route = route = Route("hip")
+    g.route = route = Route("hip", LIBS)
     g.torch = torch = route.torch
     _, sim_job, want = cpu_bytes(sim_route, SEED)
     g.scene = sc = tss.Scene(route, SEED)

@@ -19,16 +19,15 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
 import handmade_views as hv
+from route import Route, SENT
 import test_dense as td
 import test_indels as ti
 import test_select as ts
 import test_vet as tv
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_ivet")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_ivet_sim.so")
-SENT = td.SENT
+LIBS = tv.LIBS + ("ivet", "indels")
 PAD = 3
 NVAL = capi.IVET_NVAL
 ALL = ("fail", "vals", "ctl_count", "keep")
@@ -54,29 +53,14 @@ MID = dict({k: x for k, x in tv.MID.items() if k != "min_var_bq"}, min_depth=4, 
 EASY = T_(min_depth=4, min_var_count=2, freq_num=1, freq_den=20, min_var_mapq=15.0, min_ref_mapq=15.0, ctl_max_count=1, ctl_frac_num=1, ctl_frac_den=2)
 
 
-class Route(tv.Route):
-    """tv.Route (engine + dense + select + vet libraries, the memory their views live in) with the ivet and indels libraries of its kind"""
-
-    def __init__(self, name):
-        tv.Route.__init__(self, name)
-        if name == "hip":
-            self.ivet, self.indels = capi.IVet(), capi.Indels()
-            assert self.ivet.kind() == "hip-gfx950"
-        else:
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            subprocess.check_call(["make", "-s", "-C", ti.SIM_DIR], stderr=subprocess.DEVNULL)
-            self.ivet, self.indels = capi.IVet(SIM_LIB), capi.Indels(ti.SIM_LIB)
-            assert self.ivet.kind() == "sim"
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, LIBS, engine=True)
 
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS, engine=True)
 
 
 # ------------------------------------------------------------------------------------------------ tables
@@ -245,10 +229,10 @@ def call(route, v, d, T, idx=None, why=None, role=None, kinds=INS | DEL, tests=A
     n = idx.size if n is None else n
     ds = m + PAD if ds is None else ds
     w, wn = max(min(ds, m + PAD), 1), max(n, 0) + PAD
-    bf, bv, bc, bk, bs = route.sentinel(w), route.sentinel(NVAL * w), route.sentinel(w), route.sentinel(wn), route.sentinel(1)
+    bf, bv, bc, bk, bs = route.sentinel_words(w), route.sentinel_words(NVAL * w), route.sentinel_words(w), route.sentinel_words(wn), route.sentinel_words(1)
     wsb = route.ivet.workspace(v, m) if v is not None else 0
     assert wsb % 4 == 0
-    bw = route.sentinel(wsb // 4)
+    bw = route.sentinel_words(wsb // 4)
     bi = route.put(idx)
     ba = route.put(np.asarray(why, np.uint32)) if why is not None else None
     rc = route.ivet.lib.brc_ivet_records(route.ivet.h if handle else None, C.byref(v) if v is not None else None, C.byref(d) if d is not None else None,
@@ -1169,9 +1153,7 @@ def test_the_chain_select_indels_vet_indels_sites(route, two_libs):
     the reference predicate keeps"""
     from bam_readcount_amd import tensors
     import test_panel as tp
-    if route.name == "sim":
-        subprocess.check_call(["make", "-s", "-C", tp.SIM_DIR])
-    panel = capi.Panel() if route.name == "hip" else capi.Panel(tp.SIM_LIB)
+    panel = route.another("panel")
     ref, arrs, res = two_libs
     D = tv.Dense.of(res)
     T = Tab.of_oracle(res.indels)
@@ -1233,7 +1215,7 @@ def _sanitized(tmp_path, name, v, d, D, calls):
     case, out = str(tmp_path / (name + ".bin")), str(tmp_path / (name + ".res"))
     open(case, "wb").write(_serialize(v, d, calls))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    pr = subprocess.run([os.path.join(SIM_DIR, "ivet_check_asan"), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    pr = subprocess.run([side.sim_checker(side.SIDE["ivet"]), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert pr.returncode == 0, (name, pr.stderr.decode()[-3000:])
     assert pr.stdout.decode().strip() == "%d calls" % len(calls), name
     raw = np.fromfile(out, np.uint32); o = 0
@@ -1256,7 +1238,6 @@ def test_calls_under_the_host_sanitizers(sim_route, tmp_path):
     of exactly brc_ivet_workspace bytes, destinations of exactly [planes][m] and [n] — a load or store outside them is a report — and
     the results are the reference's.  Never under the gpu mark; nothing is loaded into python with a sanitizer."""
     route = sim_route
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
     rng = np.random.default_rng(2)
     some = 0
     for records in (True, False):
@@ -1293,7 +1274,7 @@ def test_calls_under_the_host_sanitizers(sim_route, tmp_path):
     # an unsorted table over linked third-allele records: in range, and exact where the contract says so (the sanitizer is the check here)
     q, U = unsorted_over_records(D)
     open(str(tmp_path / "unsorted.bin"), "wb").write(_serialize(v, d, [(U, [q, 130], None, None, INS | DEL, ALL_TESTS, 31, True, MID)]))
-    pr = subprocess.run([os.path.join(SIM_DIR, "ivet_check_asan"), str(tmp_path / "unsorted.bin"), str(tmp_path / "unsorted.res")], stdout=subprocess.PIPE,
+    pr = subprocess.run([side.sim_checker(side.SIDE["ivet"]), str(tmp_path / "unsorted.bin"), str(tmp_path / "unsorted.res")], stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert pr.returncode == 0 and pr.stdout.decode().strip() == "1 calls", pr.stderr.decode()[-3000:]
     raw = np.fromfile(str(tmp_path / "unsorted.res"), np.uint32)

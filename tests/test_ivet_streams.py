@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
+from route import Route
 import test_indels as ti
 import test_ivet as tiv
 import test_side_streams as tss
@@ -23,14 +24,7 @@ PAD = tss.PAD
 LIST = np.array([2, 63, 64, 64, 100, 255, 256, 300, 599, tss.P], np.int32)
 
 
-class Route(tss.Route):
-    def __init__(self, name):
-        tss.Route.__init__(self, name)
-        if name == "hip":
-            self.ivet = capi.IVet()
-        else:
-            tss.subprocess.check_call(["make", "-s", "-C", tiv.SIM_DIR])
-            self.ivet = capi.IVet(tiv.SIM_LIB)
+LIBS = tss.LIBS + ("ivet",)
 
 
 def chain_job(sc, expect):
@@ -76,7 +70,7 @@ def cpu_bytes(sim_route, seed):
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS)
 
 
 def test_the_chain_on_the_cpu_builds_is_the_predicate(sim_route):
@@ -107,7 +101,7 @@ def gpu(sim_route):
     """The hip route, one scene, the chain run once on the default stream (code objects loaded, the values checked there too, its warm
     host time taken), and the hold sized against it."""
     g = tss.Gpu()
-    g.route = route = Route("hip")
+    g.route = route = Route("hip", LIBS)
     g.torch = torch = route.torch
     _, _, want = cpu_bytes(sim_route, 21)
     g.scene = sc = tss.Scene(route, 21)

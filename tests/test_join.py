@@ -12,16 +12,14 @@ behind a buffer's size and every buffer that was not asked for must keep it.  Th
 Sizes that matter to the kernels (brc_join.hip): a lane stores four elements at a 16-byte boundary of its row, a wave 256, a workgroup
 1024; a row whose base is not 16-byte aligned has one to three single elements in front."""
 import ctypes as C
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
 import handmade_views as hv
+from route import Route, SENT, SENT8
 import test_dense as td
 import test_indels as ti
 import test_inorm as tn
@@ -29,61 +27,24 @@ import test_ivet as tiv
 import test_select as ts
 import test_vet as tv
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_join")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_join_sim.so")
-SENT8, SENT, NONE32, PAD = hv.SENT8, hv.SENT, hv.NONE32, hv.PAD
+NONE32, PAD = hv.NONE32, hv.PAD
 NI, NF = 9, 4
 EMPTY_SLOT = 1 | (7 << 8)             # lane2_store (brc_core.h) for a position no read covers: bucket 1, NB_NONE
 PLANES = (("ncol", 1), ("depth", 1), ("slotid", 1), ("si", 18), ("sf", 8))
 VIEW_BUFS = ("ncol", "depth", "slotid", "si", "sf", "xagg")
 INDEL_BUFS = ("slots", "seq_off", "l_qseq", "seq4", "ref")
 CASE, CTL = capi.ROLE_CASE, capi.ROLE_CONTROL
-
-
-def side(name, cls, hip):
-    """the side library `name` of one kind"""
-    if hip:
-        return cls()
-    d = os.path.join(ROOT, "tests", "sim_" + name)
-    subprocess.check_call(["make", "-s", "-C", d], stderr=subprocess.DEVNULL)
-    return cls(os.path.join(d, "libbrc_%s_sim.so" % name))
-
-
-class Route(tn.Route):
-    """tn.Route (engine, dense, select, vet, ivet, indels and inorm libraries, the memory their views live in) with the join, panel, bins
-    and runs libraries of its kind"""
-
-    def __init__(self, name):
-        tn.Route.__init__(self, name)
-        hip = name == "hip"
-        self.join, self.panel, self.bins, self.runs = side("join", capi.Join, hip), side("panel", capi.Panel, hip), side("bins", capi.Bins, hip), side("runs", capi.Runs, hip)
-        assert self.join.kind() == ("hip-gfx950" if hip else "sim")
-        assert self.mem == (capi.MEM_DEVICE if hip else capi.MEM_HOST)
-
-    # (hv.Route's helpers, which hv.make_view / hv.make_indels call)
-    def put(self, a):
-        a = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-        a = a if a.size else np.zeros(4, np.uint8)
-        return self.torch.from_numpy(a.copy()).cuda() if self.name == "hip" else a.copy()
-
-    def filled(self, n_bytes):
-        return self.put(np.full(max(n_bytes, 4), SENT8, np.uint8))
-
-    def ptr(self, buf):
-        return buf.data_ptr() if self.name == "hip" else buf.ctypes.data
-
-    def host(self, buf):
-        return buf.cpu().numpy() if self.name == "hip" else buf
+LIBS = tn.LIBS + ("join", "panel", "bins", "runs")          # (every row of the table)
 
 
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, LIBS, engine=True)
 
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS, engine=True)
 
 
 # ------------------------------------------------------------------------------------------------ sources and the reference
@@ -218,9 +179,9 @@ def run(route, srcs, pos0, n, stride=None, skew=False, seq_cap=None, halves=("vi
         z = capi.JoinSizes()
     wsb = int(z.workspace_bytes)
     assert wsb == route.join.workspace(int(z.n_slots))
-    ws = route.filled(wsb)
+    ws = route.sentinel_bytes(wsb)
     if seq_cap is None:
-        c0 = route.filled(8)
+        c0 = route.sentinel_bytes(8)
         if "indels" in halves and not rc:
             route.join.views(src, pos0, n, stride, counts=route.ptr(c0), workspace=route.ptr(ws), workspace_bytes=wsb)
             J.first_counts = route.host(c0)[:8].view(np.uint32).tolist()
@@ -231,9 +192,9 @@ def run(route, srcs, pos0, n, stride=None, skew=False, seq_cap=None, halves=("vi
     sizes["seq4"] = seq_cap
     bufs, off = {}, {}
     for k in capi.JOIN_DESTS:
-        bufs[k] = route.filled(sizes[k] + 4 * PAD + (32 if skew else 0))
+        bufs[k] = route.sentinel_bytes(sizes[k] + 4 * PAD + (32 if skew else 0))
         off[k] = ((-route.ptr(bufs[k])) % 16 + 4) if skew and k in VIEW_BUFS[:5] else 0
-    cbuf, sbuf = route.filled(8), route.filled(4)
+    cbuf, sbuf = route.sentinel_bytes(8), route.sentinel_bytes(4)
     wanted = (VIEW_BUFS if "view" in halves else ()) + (INDEL_BUFS if "indels" in halves else ())
     dest = capi.JoinDest(**{k: route.ptr(bufs[k]) + off[k] for k in wanted})
     J.view, J.indels = capi.DeviceView(), capi.DeviceIndels()
@@ -310,11 +271,11 @@ def check(route, srcs, pos0, n, what="", stride=None, **kw):
 def spelled(route, view, I, first, n):
     """brc_indels_gather over an indels view in the route's memory: (pos, lib, len, text) per record, in the table's order"""
     wsb = route.indels.workspace(view, n)
-    ws, cnt = route.filled(wsb), route.filled(8)
+    ws, cnt = route.sentinel_bytes(wsb), route.sentinel_bytes(8)
     route.indels.gather(view, first - int(view.pos0), n, workspace=route.ptr(ws), workspace_bytes=wsb, counts=route.ptr(cnt))
     m, nb = route.host(cnt)[:8].view(np.uint32).tolist()
-    b = {k: route.filled(4 * (m + 1)) for k in ("pos", "lib", "len", "allele_off")}
-    b["alleles"] = route.filled(nb)
+    b = {k: route.sentinel_bytes(4 * (m + 1)) for k in ("pos", "lib", "len", "allele_off")}
+    b["alleles"] = route.sentinel_bytes(nb)
     route.indels.gather(view, first - int(view.pos0), n, workspace=route.ptr(ws), workspace_bytes=wsb, cap=m, alleles_cap=nb, **{k: route.ptr(x) for k, x in b.items()})
     h = {k: np.array(route.host(x)) for k, x in b.items()}
     off = h["allele_off"].view(np.uint32)[:m + 1].tolist()
@@ -513,7 +474,7 @@ def test_seq_cap_one_short_counts_alone_and_two_calls(route):
     assert J.counts == J2.counts and J.status == J2.status
     # the counts alone: nothing but the two words (and the status word) is written, the host structs are not filled in
     src = capi.join_sources([(v, d) for v, d, _ in placed])
-    ws, c, st = route.filled(int(J.z.workspace_bytes)), route.filled(8 + 4 * PAD), route.filled(4)
+    ws, c, st = route.sentinel_bytes(int(J.z.workspace_bytes)), route.sentinel_bytes(8 + 4 * PAD), route.sentinel_bytes(4)
     v = capi.DeviceView(); v.n_lib = -77
     assert route.join.views_raw(src, 1000, 80, 80, out_view=v, counts=route.ptr(c), status=route.ptr(st), workspace=route.ptr(ws), workspace_bytes=int(J.z.workspace_bytes)) == 0
     assert route.host(c).view(np.uint32).tolist() == W["counts"] + [SENT] * PAD and route.host(st)[:4].view(np.uint32)[0] == 0 and v.n_lib == -77
@@ -540,8 +501,8 @@ def test_refused_calls_write_nothing(route):
 
     def refused(what, K=None, sources=src, p0=pos0, nn=n, stride=n, dest="all", view=True, indels=True, counts=True, seq_cap=None, ws=True, wsb=wsb, handle=True, drop=()):
         J = good
-        bufs = {k: route.filled(J.sizes[k] + 4 * PAD) for k in capi.JOIN_DESTS}
-        w, c, st = route.filled(wsb), route.filled(8), route.filled(4)
+        bufs = {k: route.sentinel_bytes(J.sizes[k] + 4 * PAD) for k in capi.JOIN_DESTS}
+        w, c, st = route.sentinel_bytes(wsb), route.sentinel_bytes(8), route.sentinel_bytes(4)
         d = capi.JoinDest(**{k: route.ptr(x) for k, x in bufs.items() if k not in drop}) if dest == "all" else dest
         v, i = capi.DeviceView(), capi.DeviceIndels()
         v.n_lib = i.n_lib = -77
@@ -611,7 +572,7 @@ def test_refused_calls_write_nothing(route):
     for what, k, addr in (("ncol on the source's ncol", "ncol", v0.ncol), ("sf ends inside the source's si", "sf", v0.si - good.sizes["sf"] + 4),
                           ("xagg on the source's records", "xagg", v0.xagg), ("the arena on the source's slots", "seq4", d0.slots + 71),
                           ("ref on the source's l_qseq", "ref", d0.l_qseq), ("slots on the source's reference", "slots", d0.ref - good.sizes["slots"] + 1)):
-        bufs = {x: route.filled(good.sizes[x] + 4 * PAD) for x in capi.JOIN_DESTS}
+        bufs = {x: route.sentinel_bytes(good.sizes[x] + 4 * PAD) for x in capi.JOIN_DESTS}
         d = capi.JoinDest(**dict({x: route.ptr(y) for x, y in bufs.items()}, **{k: addr}))
         before = [np.array(route.host(x)) for x in hv_buffers(keep)]
         refused(what, dest=d, seq_cap=max(good.sizes["seq4"], 1))
@@ -836,7 +797,7 @@ def test_tensors_join_errors(route, split_batch):
         with pytest.raises(ValueError):
             tensors.join(bad.pop("engines", Bs), route.join, **bad)
     if route.name == "hip":                                              # a mix of host and device engines
-        sim = Route("sim")
+        sim = Route("sim", engine=True)
         H = td.computed(sim.engine_lib, one_library(arrs, 0), 50, 500, ref)
         with pytest.raises(ValueError):
             tensors.join([Bs[0], H], route.join)

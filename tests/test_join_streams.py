@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
+from route import Route
 import test_dense as td
 import test_join as tj
 import test_side_streams as tss
@@ -27,10 +28,7 @@ ROLE, SEL_P = [1, 2, 1, 2], tss.SEL_P
 KINDS = ("istat", "fstat", "depth", "ncol", "unavail")
 
 
-class Route(tss.Route):
-    def __init__(self, name):
-        tss.Route.__init__(self, name)
-        self.join = tj.side("join", capi.Join, name == "hip")
+LIBS = tss.LIBS + ("join",)
 
 
 def sources_of(sc):
@@ -41,9 +39,9 @@ def counted(route, sc):
     """the first, untimed call: the join for its two counts alone, on the default stream; the host reads them"""
     src = sources_of(sc)
     z = route.join.sizes(src, POS0, N, N)
-    ws, c = route.alloc(int(z.workspace_bytes)), route.alloc(8)
+    ws, c = route.sentinel_bytes(max(int(z.workspace_bytes), 8)), route.sentinel_bytes(8)
     route.join.views(src, POS0, N, N, counts=route.ptr(c), workspace=route.ptr(ws), workspace_bytes=int(z.workspace_bytes))
-    return z, [int(x) for x in route.bytes_of(c)[:8].view(np.uint32)]
+    return z, [int(x) for x in route.host(c)[:8].view(np.uint32)]
 
 
 def chain_job(sc, expect):
@@ -95,7 +93,7 @@ def cpu_bytes(sim_route, seed):
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS)
 
 
 def test_the_chain_on_the_cpu_builds_is_the_reference(sim_route):
@@ -134,7 +132,7 @@ def gpu(sim_route):
     """The hip route, one scene, the chain run once on the default stream (code objects loaded, the values checked there too, its warm
     host time taken), and the hold sized against it."""
     g = tss.Gpu()
-    g.route = route = Route("hip")
+    g.route = route = Route("hip", LIBS)
     g.torch = torch = route.torch
     _, sim_job, want = cpu_bytes(sim_route, SEED)
     g.scene = sc = tss.Scene(route, SEED)

@@ -18,48 +18,21 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+import abi_side as side
+from route import Route, SENT
 import test_dense as td
 import test_indels as ti
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_panel")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_panel_sim.so")
-SENT = td.SENT
 KINDS = td.KINDS
 OOR, DESC = 1, 2
 planes_of = td.planes_of
 PER_LIB = dict(lib_names=["libA", "libB"], per_lib=True)
 
 
-class Route(td.Route):
-    """td.Route (engine + dense libraries, the memory their views live in) with the panel and the indels library of the same kind"""
-
-    def __init__(self, name):
-        td.Route.__init__(self, name)
-        if name == "hip":
-            self.panel = capi.Panel()
-            self.indels = capi.Indels()
-            assert self.panel.kind() == "hip-gfx950"
-        else:
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            subprocess.check_call(["make", "-s", "-C", ti.SIM_DIR], stderr=subprocess.DEVNULL)
-            self.panel = capi.Panel(SIM_LIB)
-            self.indels = capi.Indels(ti.SIM_LIB)
-            assert self.panel.kind() == "sim"
-
-    def ints(self, a):
-        """an int32 list in the memory of this route's views (never empty: an empty list still has an address)"""
-        a = np.ascontiguousarray(a, np.int32)
-        a = a if a.size else np.zeros(1, np.int32)
-        return self.torch.from_numpy(a).cuda() if self.name == "hip" else a
-
-    def host(self, a):
-        return a.cpu().numpy() if self.name == "hip" else a
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, ("dense", "panel", "indels"), engine=True)
 
 
 def gather(route, view, idx, ds, kinds=KINDS, n=None, status=True, no_idx=False, handle=True, words=None):
@@ -68,8 +41,8 @@ def gather(route, view, idx, ds, kinds=KINDS, n=None, status=True, no_idx=False,
     L = int(view.n_lib) if view is not None and view.n_lib > 0 else 1
     n = len(idx) if n is None else n
     size = {k: planes_of(k, L) * max(ds, 0) if words is None else words for k in kinds}
-    bufs = {k: route.sentinel(size[k]) for k in kinds}
-    st = route.sentinel(1)
+    bufs = {k: route.sentinel_words(size[k]) for k in kinds}
+    st = route.sentinel_words(1)
     ibuf = route.ints(idx)
     fn = route.panel.lib.brc_panel_gather
     args = {k: route.ptr(b) for k, b in bufs.items()}
@@ -323,7 +296,7 @@ def test_lists_under_the_host_sanitizers(oracle_lib, sim_lib, tmp_path, monkeypa
     """The lists of tests 1, 2 and 4 on the CPU build with -fsanitize=address,undefined: sources of exactly the view's sizes, lists of
     exactly n indices, destinations of exactly (planes - 1) * dst_stride + n elements — a load or store outside them is a report —
     and whatever the contract promises about the results holds."""
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
+    checker = side.sim_checker(side.SIDE["panel"])
     monkeypatch.setenv("BRC_FORCE_DOM", "3"); monkeypatch.setenv("BRC_XEV_CAP", "1")
     ref, arrs = td.third_allele_inputs()
     res, _ = td.oracle_result(oracle_lib, arrs, 100, 1900, ref, **PER_LIB)
@@ -335,7 +308,7 @@ def test_lists_under_the_host_sanitizers(oracle_lib, sim_lib, tmp_path, monkeypa
     open(tmp_path / "case.bin", "wb").write(_serialize(v, [(idx, ds) for idx, ds, _ in lists]))
     eng.close()
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([os.path.join(SIM_DIR, "panel_check_asan"), str(tmp_path / "case.bin"), str(tmp_path / "res.bin")],
+    p = subprocess.run([checker, str(tmp_path / "case.bin"), str(tmp_path / "res.bin")],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     assert p.stdout.decode().strip() == "%d lists" % len(lists)
@@ -427,7 +400,7 @@ def test_tensors_sites_arguments(route, oracle_lib):
     e = tensors.sites(eng, route.panel, positions=[], want=("depth",), indels=route.indels)
     assert e["n"] == 0 and tuple(e["depth"].shape) == (2, 0) and e["indels"]["m"] == 0
     # host lists are checked before anything is queued
-    untouched = route.sentinel(2 * len(pos))
+    untouched = route.sentinel_words(2 * len(pos))
     keep = untouched.view(route.torch.uint32).view(2, len(pos)) if route.name == "hip" else untouched.reshape(2, len(pos))
     for bad in (dict(positions=pos[::-1]), dict(positions=[res.pos0 - 1] + pos[1:]), dict(positions=pos[:-1] + [res.pos0 + res.n_pos]),
                 dict(windows=(np.array([300, 200], np.int32), np.array([301, 204], np.int32))), dict(windows=(np.array([300], np.int32), np.array([299], np.int32))),

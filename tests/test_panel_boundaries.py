@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import handmade_views as hv
+from route import Route
 
 KINDS = hv.KINDS
 L, P = 3, 513
@@ -20,7 +21,7 @@ K_REC = (5, 100, 101, 300, P - 1)          # the positions that carry third-alle
 
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return hv.Route(request.param, ("dense", "panel"))
+    return Route(request.param, ("dense", "panel"))
 
 
 _case = []

@@ -24,14 +24,13 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import Route, SENT
 import synth
 import test_dense as td
 import test_select as ts
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_runs")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_runs_sim.so")
-SENT = td.SENT
+LIBS = ("dense", "select", "runs")
 SENT64 = np.uint64(0xA5A5A5A5A5A5A5A5)
 PAD = 3                                   # elements of every destination behind what the contract writes
 MAXC = capi.RUNS_MAX_CUT + 2              # the most classes a call can have
@@ -40,28 +39,14 @@ ALL = ("start", "end", "cls", "counts", "per_class")
 PER_LIB = ts.PER_LIB
 
 
-class Route(ts.Route):
-    """ts.Route (engine + dense + select libraries, the memory their views live in) with the runs library of the same kind"""
-
-    def __init__(self, name):
-        ts.Route.__init__(self, name)
-        if name == "hip":
-            self.runs = capi.Runs()
-            assert self.runs.kind() == "hip-gfx950"
-        else:
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            self.runs = capi.Runs(SIM_LIB)
-            assert self.runs.kind() == "sim"
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, LIBS, engine=True)
 
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS, engine=True)
 
 
 # ------------------------------------------------------------------------------------------------ the reference
@@ -106,10 +91,10 @@ def call(route, v, d, k0, n, cap, cuts=(1,), combine=MIN, role=None, keep=None, 
     for k, x in (fields or {}).items():
         setattr(par, k, x)
     c = max(cap, 0)
-    bs, be, bc, bn, bp = route.sentinel(c + PAD), route.sentinel(c + PAD), route.sentinel(c + PAD), route.sentinel(1), route.sentinel(2 * (MAXC + PAD))
+    bs, be, bc, bn, bp = route.sentinel_words(c + PAD), route.sentinel_words(c + PAD), route.sentinel_words(c + PAD), route.sentinel_words(1), route.sentinel_words(2 * (MAXC + PAD))
     wsb = route.runs.workspace(n)
     assert wsb % 4 == 0 and wsb == (4 * n + 8 * ((n + 255) // 256) if n > 0 else 0)
-    bw = route.sentinel(wsb // 4)
+    bw = route.sentinel_words(wsb // 4)
     rc = route.runs.lib.brc_runs_find(route.runs.h if handle else None, C.byref(v) if v is not None else None, C.byref(d) if d is not None else None,
                                       C.byref(par) if params else None, k0, n, cap, route.ptr(bs) if "start" in want else None,
                                       route.ptr(be) if "end" in want else None, route.ptr(bc) if "cls" in want else None,
@@ -547,9 +532,7 @@ def test_tensors_runs_names_and_the_chain_into_bins(route, oracle_lib, low_regio
     tensors.bins: the bins' depth sums equal the reference's over those intervals"""
     from bam_readcount_amd import tensors
     import test_bins as tb
-    if route.name == "sim":
-        subprocess.check_call(["make", "-s", "-C", tb.SIM_DIR])
-    bins = capi.Bins() if route.name == "hip" else capi.Bins(tb.SIM_LIB)
+    bins = route.another("bins")
     ref, arrs, res = low_region
     names = PER_LIB["lib_names"]
     D = ts.Dense.of(res)
@@ -620,7 +603,7 @@ def _sanitized(tmp_path, name, v, d, D, calls):
     case, out = str(tmp_path / (name + ".bin")), str(tmp_path / (name + ".res"))
     open(case, "wb").write(_serialize(v, d, calls))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    pr = subprocess.run([os.path.join(SIM_DIR, "runs_check_asan"), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    pr = subprocess.run([side.sim_checker(side.SIDE["runs"]), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert pr.returncode == 0, (name, pr.stderr.decode()[-3000:])
     assert pr.stdout.decode().strip() == "%d calls" % len(calls), name
     raw = open(out, "rb").read(); o = 0
@@ -665,7 +648,6 @@ def test_calls_under_the_host_sanitizers(sim_route, tmp_path):
     of the device's k_runs_parts alone, which the CPU build does not have.  Never under the gpu mark; nothing is loaded into python
     with a sanitizer."""
     route = sim_route
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
     some = 0
     wins = ts.window_list(SHAPE_P) + [(64, 192), (256, 256), (263, 1)]
     for i, (name, (depth, keep)) in enumerate(shape_depths().items()):

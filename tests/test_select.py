@@ -26,13 +26,11 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import Route, SENT
 import synth
 import test_dense as td
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_select")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_select_sim.so")
-SENT = td.SENT
 PAD = 3                                   # elements of idx / why behind `cap`
 SNV, INDEL, BOTH = capi.SELECT_SNV, capi.SELECT_INDEL, capi.SELECT_SNV | capi.SELECT_INDEL
 U32 = 2 ** 32 - 1
@@ -43,34 +41,12 @@ def P_(flags=BOTH, min_depth=0, min_alt=1, frac=(0, 1), ctl_min_depth=0, ctl_max
     return dict(flags=flags, min_depth=min_depth, min_alt=min_alt, frac=frac, ctl_min_depth=ctl_min_depth, ctl_max_alt=ctl_max_alt, ctl_frac=ctl_frac)
 
 
-class Route(td.Route):
-    """td.Route (engine + dense libraries, the memory their views live in) with the select library of the same kind"""
-
-    def __init__(self, name):
-        td.Route.__init__(self, name)
-        if name == "hip":
-            self.select = capi.Select()
-            assert self.select.kind() == "hip-gfx950"
-        else:
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            self.select = capi.Select(SIM_LIB)
-            assert self.select.kind() == "sim"
-
-    def put(self, a):
-        """a numpy array in the memory of this route's views (hip: a torch tensor of its bytes); never empty"""
-        a = np.ascontiguousarray(a)
-        if self.name != "hip":
-            return a
-        b = a.view(np.uint8).reshape(-1)
-        return self.torch.from_numpy(b if b.size else np.zeros(4, np.uint8)).cuda()
-
-    def host(self, a):
-        return a.cpu().numpy() if self.name == "hip" else a
+LIBS = ("dense", "select")
 
 
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, LIBS, engine=True)
 
 
 # ------------------------------------------------------------------------------------------------ the reference predicate
@@ -138,9 +114,9 @@ def call(route, v, d, role, p, k0, n, cap, want=("idx", "why", "counts"), handle
     returns (rc, counts word, idx words, why words)"""
     par, keep = capi.select_params(role, p["flags"], p["min_depth"], p["min_alt"], p["frac"], p["ctl_min_depth"], p["ctl_max_alt"], p["ctl_frac"])
     c = max(cap, 0)
-    bi, bw, bc = route.sentinel(c + PAD), route.sentinel(c + PAD), route.sentinel(1)
+    bi, bw, bc = route.sentinel_words(c + PAD), route.sentinel_words(c + PAD), route.sentinel_words(1)
     wsb = route.select.workspace(v, d, n) if v is not None and d is not None else 0
-    bs = route.sentinel(wsb // 4)
+    bs = route.sentinel_words(wsb // 4)
     assert wsb % 4 == 0
     rc = route.select.lib.brc_select_sites(route.select.h if handle else None, C.byref(v) if v is not None else None, C.byref(d) if d is not None else None,
                                            C.byref(par) if params else None, k0, n, cap, route.ptr(bi) if "idx" in want else None,
@@ -505,7 +481,7 @@ def test_thresholds_met_exactly(route):
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS, engine=True)
 
 
 BIG_SETS = [P_(SNV, min_depth=U32, min_alt=2 ** 31, frac=(U32 - 1, U32), ctl_frac=(1, 4)), P_(SNV, min_alt=U32 - 5 * 2 ** 26, frac=(2 ** 31, U32)),
@@ -848,7 +824,7 @@ def _sanitized(tmp_path, name, v, d, dense, calls):
     case, out = str(tmp_path / (name + ".bin")), str(tmp_path / (name + ".res"))
     open(case, "wb").write(_serialize(v, d, calls))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    pr = subprocess.run([os.path.join(SIM_DIR, "select_check_asan"), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    pr = subprocess.run([side.sim_checker(side.SIDE["select"]), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert pr.returncode == 0, (name, pr.stderr.decode()[-3000:])
     assert pr.stdout.decode().strip() == "%d calls" % len(calls), name
     out = np.fromfile(out, np.uint32); o = 0
@@ -889,7 +865,6 @@ def test_calls_under_the_host_sanitizers(oracle_lib, sim_route, low_region, tmp_
     region of the scan carry stays with the plain routes: the carry is a loop of the device's k_select_parts alone, which the CPU
     build does not have."""
     route = sim_route
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
     some = 0
     # 2 + the windows of 3 + 6: the third-allele region
     monkeypatch.setenv("BRC_FORCE_DOM", "3"); monkeypatch.setenv("BRC_XEV_CAP", "1")
@@ -992,9 +967,7 @@ def test_tensors_select_names_errors_and_the_chain_to_sites(route, oracle_lib, t
     oracle-selected positions bit for bit"""
     from bam_readcount_amd import tensors
     import test_panel as tp
-    if route.name == "sim":
-        subprocess.check_call(["make", "-s", "-C", tp.SIM_DIR])
-    panel = capi.Panel() if route.name == "hip" else capi.Panel(tp.SIM_LIB)
+    panel = route.another("panel")
     p = TWOLIB_PARAMS[2][1]
     kw = dict(min_depth=p["min_depth"], min_alt=p["min_alt"], min_frac=p["frac"], ctl_max_frac=p["ctl_frac"])
 

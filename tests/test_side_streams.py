@@ -45,6 +45,7 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
+from route import Route, SENT8
 import synth
 import test_bins as tb
 import test_dense as td
@@ -57,7 +58,6 @@ import test_vet as tv
 P, POS0, L = 600, 1000, 2                 # three workgroups of 256 positions, two libraries
 K0, N = 5, 590                            # the window of the calls: off the 64-grid at both ends
 PAD = 3
-SENT8 = 0xA5
 REF_SLICE = (10, 580)                     # the reference slice covers plane positions [10, 580)
 INDELS = [(2, 0, 1, 5), (5, 0, 2, 3), (63, 1, -1, 2), (64, 0, -3, 4), (255, 0, 4, 5), (256, 0, 1, 3), (256, 0, -2, 2), (300, 0, 3, 2), (300, 0, 2, 4),
           (300, 1, 2, 1), (599, 1, -1, 1)]                                  # (plane index, library, length, reads)
@@ -71,28 +71,14 @@ LATE = ("depth", "ncol", "si", "ref", "slots", "idx", "edges")
 HOLD_FLOOR, HOLD_CAP = 0.05, 0.25         # seconds
 
 
-class Route(tr.Route):
-    """test_runs.Route (engine + dense + select + runs) with the bins, panel, indels and vet libraries of the same kind, and a second
-    handle of the two libraries that take a workspace"""
+LIBS = ("dense", "select", "runs", "bins", "panel", "indels", "vet")          # what a Scene's jobs call
 
-    def __init__(self, name):
-        tr.Route.__init__(self, name)
-        if name == "hip":
-            self.bins, self.panel, self.indels, self.vet = capi.Bins(), capi.Panel(), capi.Indels(), capi.Vet()
-            self.select2, self.runs2 = capi.Select(), capi.Runs()
-        else:
-            for m in (tb, tp, ti, tv):
-                subprocess.check_call(["make", "-s", "-C", m.SIM_DIR], stderr=subprocess.DEVNULL)
-            self.bins, self.panel, self.indels, self.vet = capi.Bins(tb.SIM_LIB), capi.Panel(tp.SIM_LIB), capi.Indels(ti.SIM_LIB), capi.Vet(tv.SIM_LIB)
-            self.select2, self.runs2 = capi.Select(ts.SIM_LIB), capi.Runs(tr.SIM_LIB)
 
-    def alloc(self, n_bytes):
-        """n_bytes (at least 8) bytes of 0xA5 in the memory of this route's views"""
-        a = np.full(max(n_bytes, 8), SENT8, np.uint8)
-        return self.torch.from_numpy(a).cuda() if self.name == "hip" else a
-
-    def bytes_of(self, buf):
-        return buf.cpu().numpy() if self.name == "hip" else buf
+def _route(name):
+    """LIBS and the engine, with a second handle of the two libraries that take a workspace"""
+    r = Route(name, LIBS, engine=True)
+    r.select2, r.runs2 = r.another("select"), r.another("runs")
+    return r
 
 
 # ------------------------------------------------------------------------------------------------ the views, real and decoy
@@ -502,11 +488,11 @@ ALL_JOBS = dict(SINGLE, **EARLY, **CHAINS)
 def run_plain(route, job, stream=None):
     """the job into 0xA5-filled buffers; returns (the code, {buffer: bytes}, the host's seconds inside the call)"""
     sizes = job.sizes(route)
-    buf = {k: route.alloc(n) for k, n in sizes.items()}
+    buf = {k: route.sentinel_bytes(max(n, 8)) for k, n in sizes.items()}
     t0 = time.perf_counter()
     rc = job.enqueue(route, buf, stream)
     dt = time.perf_counter() - t0
-    return rc, {k: route.bytes_of(b)[:sizes[k]] for k, b in buf.items()}, dt
+    return rc, {k: route.host(b)[:sizes[k]] for k, b in buf.items()}, dt
 
 
 def compare(got, want, what):
@@ -519,7 +505,7 @@ def compare(got, want, what):
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return _route("sim")
 
 
 def test_the_decoy_reference_differs_in_every_compared_output(sim_route):
@@ -691,7 +677,7 @@ def gpu():
     """The hip route, two scenes, every job run once on the default stream (code objects and torch's kernels loaded, the values
     checked there too, the six calls' warm host times and byte counts taken), and the hold sized against them."""
     g = Gpu()
-    g.route = route = Route("hip")
+    g.route = route = _route("hip")
     g.torch = torch = route.torch
     g.scenes = [Scene(route, 21), Scene(route, 22)]
     g.call_s, g.bytes = {}, {}

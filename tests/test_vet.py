@@ -22,13 +22,12 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
-from conftest import ROOT
+import abi_side as side
+from route import Route, SENT
 import test_dense as td
 import test_select as ts
 
-SIM_DIR = os.path.join(ROOT, "tests", "sim_vet")
-SIM_LIB = os.path.join(SIM_DIR, "libbrc_vet_sim.so")
-SENT = td.SENT
+LIBS = ("dense", "select", "vet")
 PAD = 3
 NVAL = capi.VET_NVAL
 ALL = ("fail", "keep", "vals")
@@ -50,28 +49,14 @@ def T_(**kw):
     return dict(OPEN, **kw)
 
 
-class Route(ts.Route):
-    """ts.Route (engine + dense + select libraries, the memory their views live in) with the vet library of the same kind"""
-
-    def __init__(self, name):
-        ts.Route.__init__(self, name)
-        if name == "hip":
-            self.vet = capi.Vet()
-            assert self.vet.kind() == "hip-gfx950"
-        else:
-            subprocess.check_call(["make", "-s", "-C", SIM_DIR])
-            self.vet = capi.Vet(SIM_LIB)
-            assert self.vet.kind() == "sim"
-
-
 @pytest.fixture(scope="module", params=["sim", pytest.param("hip", marks=pytest.mark.gpu)])
 def route(request):
-    return Route(request.param)
+    return Route(request.param, LIBS, engine=True)
 
 
 @pytest.fixture(scope="module")
 def sim_route():
-    return Route("sim")
+    return Route("sim", LIBS, engine=True)
 
 
 # ------------------------------------------------------------------------------------------------ the reference predicate
@@ -171,10 +156,10 @@ def call(route, v, d, idx, alt=None, lib_on=None, tests=capi.VET_ALL_TESTS, want
     ds = max(n, 0) + PAD if ds is None else ds
     L = int(v.n_lib) if v is not None and 0 < v.n_lib < 1000 else 1
     w = max(ds, 1)
-    bf, bk, bv, bs = route.sentinel(L * 4 * w), route.sentinel(w), route.sentinel(L * 4 * NVAL * w), route.sentinel(1)
+    bf, bk, bv, bs = route.sentinel_words(L * 4 * w), route.sentinel_words(w), route.sentinel_words(L * 4 * NVAL * w), route.sentinel_words(1)
     wsb = route.vet.workspace(v, n) if v is not None else 0
     assert wsb % 4 == 0
-    bw = route.sentinel(wsb // 4)
+    bw = route.sentinel_words(wsb // 4)
     bi = route.put(idx)
     ba = route.put(np.asarray(alt, np.uint32)) if alt is not None else None
     rc = route.vet.lib.brc_vet_sites(route.vet.h if handle else None, C.byref(v) if v is not None else None, C.byref(d) if d is not None else None,
@@ -930,9 +915,7 @@ def test_the_chain_select_vet_sites(route, oracle_lib, low_region):
     throughout on the GPU route: the panel holds the oracle's planes at the positions the reference predicate keeps"""
     from bam_readcount_amd import tensors
     import test_panel as tp
-    if route.name == "sim":
-        subprocess.check_call(["make", "-s", "-C", tp.SIM_DIR])
-    panel = capi.Panel() if route.name == "hip" else capi.Panel(tp.SIM_LIB)
+    panel = route.another("panel")
     ref, arrs, res = low_region
     D = Dense.of(res)
     eng = td.computed(route.engine_lib, arrs, 50, 2950, ref, **PER_LIB)
@@ -977,7 +960,7 @@ def _sanitized(tmp_path, name, v, d, D, calls):
     case, out = str(tmp_path / (name + ".bin")), str(tmp_path / (name + ".res"))
     open(case, "wb").write(_serialize(v, d, calls))
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    pr = subprocess.run([os.path.join(SIM_DIR, "vet_check_asan"), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
+    pr = subprocess.run([side.sim_checker(side.SIDE["vet"]), case, out], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
     assert pr.returncode == 0, (name, pr.stderr.decode()[-3000:])
     assert pr.stdout.decode().strip() == "%d calls" % len(calls), name
     raw = np.fromfile(out, np.uint32); o = 0
@@ -1002,7 +985,6 @@ def test_calls_under_the_host_sanitizers(sim_route, tmp_path):
     brc_vet_workspace bytes, destinations of exactly [planes][n] — a load or store outside them is a report — and the results are the
     reference's.  Never under the gpu mark; nothing is loaded into python with a sanitizer."""
     route = sim_route
-    subprocess.check_call(["make", "-s", "-C", SIM_DIR, "asan"])
     rng = np.random.default_rng(2)
     some = 0
     for records in (True, False):

@@ -8,18 +8,13 @@ import numpy as np
 import pytest
 
 from bam_readcount_amd import capi
+from route import Route
 import test_dense as td
 import test_side_streams as ss
 import test_vet as tv
 
 PAD = ss.PAD
 T = tv.T_(min_depth=4, min_var_count=2, freq_num=1, freq_den=8)
-
-
-class Route(ss.Route):
-    def __init__(self, name):
-        ss.Route.__init__(self, name)
-        self.vet = tv.Route(name).vet
 
 
 def chain(sc, cap):
@@ -47,16 +42,16 @@ def chain(sc, cap):
 
 @pytest.mark.gpu
 def test_select_vet_panel_back_to_back_on_a_held_stream():
-    sim, hip = Route("sim"), Route("hip")
+    sim, hip = Route("sim", ss.LIBS), Route("hip", ss.LIBS)
     torch = hip.torch
     # the CPU route: the same views (the scene is seeded), the same calls
     sc = ss.Scene(sim, 21)
     cap = ss.select_job(sc).cap
     sizes, enqueue = chain(sc, cap)
     want_sizes = sizes(sim)
-    buf = {k: sim.alloc(n) for k, n in want_sizes.items()}
+    buf = {k: sim.sentinel_bytes(max(n, 8)) for k, n in want_sizes.items()}
     assert enqueue(sim, buf, None) == 0
-    want = {k: sim.bytes_of(b)[:want_sizes[k]].copy() for k, b in buf.items() if not k.endswith("ws")}
+    want = {k: sim.host(b)[:want_sizes[k]].copy() for k, b in buf.items() if not k.endswith("ws")}
     keep = want["v.keep"].view(np.uint32)[:cap]
     assert cap >= 3 and (keep != 0).any() and (keep == 0).any() and sc.v.n_xagg > 0
     # the GPU route: once on the default stream (code objects loaded), then held
