@@ -8,6 +8,8 @@
               tests on listed candidates, libbrc_vet_hip.so), vet_indels (the same tests and an allele-aware control veto on
               the records of the indel table, libbrc_ivet_hip.so) and normalize_indels (the indel table left-aligned against
               the reference and its equal records merged, libbrc_inorm_hip.so)
+    consensus the binding of the consensus caller (libbrc_cons_hip.so); tensors.consensus is the function over it: a region and its
+              indel table turned into a sequence, the per-position calls and the liftover offsets
     shard     splitting a run over ranks / GPUs
 
 Submodules are imported on first use (`from bam_readcount_amd import tensors`); importing the package loads no native library and
@@ -15,7 +17,7 @@ needs neither torch nor a GPU.
 """
 import importlib
 
-__all__ = ["capi", "tensors", "shard"]
+__all__ = ["capi", "tensors", "shard", "consensus"]
 
 
 def __getattr__(name):

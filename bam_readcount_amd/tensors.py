@@ -55,12 +55,18 @@ engine-like object — the libraries of the second behind those of the first —
 by libbrc_join_hip.so (capi.Join):
     both = tensors.join([tumour_eng, normal_eng], capi.Join(), names=["tumour", "normal"])
     sel = tensors.select(both, select, case=["tumour"], control=["normal"], min_depth=10, min_alt=3)
+
+A region becomes a SEQUENCE with consensus(): one call per position from the pooled counts of A C G T and of the reads that carry a
+deletion across it (which only the indel table knows), accepted insertions behind their anchors, and the offset of every reference
+position in the sequence, by libbrc_cons_hip.so (consensus.Cons):
+    c = tensors.consensus(eng, consensus.Cons(), table=tensors.normalize_indels(eng, inorm, tensors.indels(eng, lib)), min_depth=4)
 """
 from functools import lru_cache, partial
 
 import numpy as np
 
 from . import capi
+from . import consensus as cons_api
 
 
 # ------------------------------------------------------------------------------------------------ the memory the results lie in
@@ -1102,3 +1108,102 @@ def join(engines, join, names=None, beg0=None, end=None):
         arrays["seq4"] = mem.empty((0,), np.uint8)
         call(seq_cap=0, seq4=mem.ptr(arrays["seq4"]))
     return Joined(view, indels, [x.encode() for x in lib_names], arrays, status, counts_out)
+
+
+CONS_KINDS = ("seq", "off", "call", "cnt", "ins_rec")
+_CONS_NEED = ("pos", "lib", "len", "istat", "allele_off", "alleles")
+
+
+def cons_shapes(n, seq_bytes):
+    """kind -> (shape, numpy dtype) of consensus()'s arrays for a window of n positions and a sequence of seq_bytes bytes"""
+    return {"seq": ((seq_bytes,), np.uint8), "off": ((n + 1,), np.uint32), "call": ((n,), np.uint8), "cnt": ((cons_api.CONS_NCNT, n), np.uint32),
+            "ins_rec": ((n,), np.uint32)}
+
+
+def _fraction(x, what):
+    try:
+        num, den = x
+    except (TypeError, ValueError):
+        raise ValueError("%s: a pair (numerator, denominator)" % what)
+    num, den = _u32(num, what), _u32(den, what)
+    if not 1 <= den <= 65535 or num > den:
+        raise ValueError("%s: a fraction of at most 1 with a denominator in [1, 65535]" % what)
+    return num, den
+
+
+def _character(x, what):
+    if isinstance(x, str):
+        x = x.encode("latin-1")
+    if isinstance(x, bytes) and len(x) == 1:
+        return x[0]
+    raise ValueError("%s: one character" % what)
+
+
+def consensus(engine, cons, *, table=None, indels=None, libs=None, min_depth, min_count=1, frac=(1, 2), ins_min_count=None, ins_frac=None,
+              aligned=False, fill="N", gap="-", ins_centric=False, beg0=None, end=None, want=CONS_KINDS):
+    """The CONSENSUS SEQUENCE of the reference positions [beg0, end) of the engine's last computed region (clipped as region() clips) —
+    include/brc_cons.h has the exact rule: per position, pooled over the counted libraries, the read counts c of A C G T and d, the
+    reads that carry a deletion across it (the deletion records of the table, each covering the |len| positions behind its anchor);
+    T = their sum; a count x qualifies when x >= min_count and x / T >= frac.  The position is uncalled below min_depth, deleted when d
+    qualifies and exceeds every base, otherwise the IUPAC code of the qualifying bases.  Behind a position the insertion with the
+    largest support (its text's counts pooled over the counted libraries) is placed when it reaches ins_min_count and ins_frac of the
+    depth.
+
+    engine: an engine or a Joined.
+    table: what indels() or normalize_indels() returned (better the second: it pools the placements of one event in a repeat), of the
+         whole view or at least of every deletion that reaches into the window; None: gathered over the whole view through `indels`
+         (a capi.Indels handle; one more synchronisation).
+    libs: the counted libraries, by the engine's library names or by number (None: all).
+    ins_min_count, ins_frac: None: min_count and frac.
+    aligned: one byte per position — `gap` on deleted positions, no insertion —, so the sequence has n bytes and NOTHING SYNCHRONISES.
+    fill: the character of an uncalled position, or "ref": the reference's own character there ('N' where there is none).
+    ins_centric: the engine was configured insertion-centric (the anchor's base counts exclude the insertion's reads).
+
+    Returns every kind in `want` (CONS_KINDS) — "seq": uint8 [counts] the sequence; "off": uint32 [n + 1] the offset in it of every
+    position's first byte (off[n] = its length): the liftover map; "call": uint8 [n] one byte per position; "cnt": uint32 [6, n] the low
+    32 bits of c[A], c[C], c[G], c[T], d and the chosen insertion's support (consensus.CONS_C_NAMES); "ins_rec": uint32 [n] the table
+    index of the accepted insertion, consensus.CONS_NO_INS where there is none — plus "status" (one uint32 element in the arrays'
+    memory: consensus.CONS_TABLE_* bits, written by the kernels, not read by this call), "m" (table records) and the ints "first", "n".
+    With the HIP libraries the arrays are torch tensors on the engine's device, filled on torch's current stream, the scratch comes from
+    torch.empty; with the CPU builds they are numpy arrays.
+
+    SYNCHRONISES ONCE unless aligned: the sequence's length is data.  A first call asks for the count alone, the host reads it (as
+    torch.nonzero does), then the sequence is allocated exactly and a second call fills everything without another wait.
+    ValueError for what the library would refuse, before anything is queued."""
+    want = _check_want(want, CONS_KINDS)
+    num, den = _fraction(frac, "frac")
+    inum, iden = (num, den) if ins_frac is None else _fraction(ins_frac, "ins_frac")
+    min_depth, min_count = _u32(min_depth, "min_depth"), _u32(min_count, "min_count")
+    ins_min_count = min_count if ins_min_count is None else _u32(ins_min_count, "ins_min_count")
+    flags = (cons_api.CONS_ALIGNED if aligned else 0) | (cons_api.CONS_INS_CENTRIC if ins_centric else 0)
+    if fill == "ref":
+        flags |= cons_api.CONS_FILL_REF
+        fill = "N"
+    fill, gap = _character(fill, "fill"), _character(gap, "gap")
+    if table is None:
+        if indels is None:
+            raise ValueError("consensus needs the indel table: table=, or indels= (a capi.Indels handle) to gather it")
+        table = globals()["indels"](engine, indels, want=_CONS_NEED)
+    v, d = engine.device_view(), engine.device_indels()
+    L = int(v.n_lib)
+    if L > cons_api.CONS_MAX_LIB:
+        raise ValueError("the consensus caller takes at most %d libraries" % cons_api.CONS_MAX_LIB)
+    mem = _memory(v)
+    params, keepalive = cons_api.cons_params(_counted(engine, L, libs), flags, min_depth, min_count, (num, den), ins_min_count, (inum, iden), fill, gap)
+    m, held = _table_arrays(mem, table, _CONS_NEED, ())
+    tab = cons_api.ConsTable(m, m, alleles_len=int(held["alleles"].shape[0]))
+    for k in ("pos", "lib", "len", "allele_off", "alleles"):
+        setattr(tab, k, mem.ptr(held[k]))
+    tab.count = mem.ptr(held["istat"])                            # (row I_N = 0 of the contiguous [9, m] planes)
+    k0, n = _window(v, beg0, end)
+    wsb = cons.workspace(v, n, m)
+    ws, status = _scratch(mem, wsb), mem.zeros(1, np.uint32)
+    call = partial(cons.call, v, d, params, tab, k0, n, n, status=mem.ptr(status), workspace=mem.ptr(ws), stream=mem.stream)
+    if aligned:                                                   # NOTHING SYNCHRONISES: the sequence has n bytes
+        arrays = _arrays(mem, cons_shapes(n, n), want)
+        if want:
+            call(seq_cap=n, **_ptrs(mem, arrays))
+    else:                                                         # ONE WAIT: the sequence's length is data
+        _, arrays = _sized_by_data(mem, call, 1, partial(cons_shapes, n), want, ("seq_cap",), fill_empty=True)
+    del keepalive, held
+    return dict({"first": int(v.pos0) + k0, "n": n, "m": m, "status": status}, **arrays)
